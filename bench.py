@@ -31,7 +31,22 @@ Ring position j looks from angle (49 j mod 80) / 80 of the circle (--ring-order 
 rank's contiguous slice samples the whole circle: per-slice train-call times at N = 8 differ by
 0.5 % instead of 3.5 % with angle j (tools/shard_balance.py, profiles/r04b_shard_balance.json).
 
-Extra objects on the JSON line:
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps (no
+events inside them), the outputs of `--dump-outputs DIR` if asked for, and the JSON line (`value`,
+`ms_per_step` and the configuration; the objects below are null). Everything else -- the train
+kernel's hipEvents inside the timed region, the per-step event times (`value_median`,
+`ms_per_step_median`, `ms_per_step_min_max`), the untimed replays (work statistics, canonical
+kernel time, `value_exit_off`), the per-rank times and the CPU baseline -- runs under `--full`,
+where `--kernel-timing`, `--timing-every`, `--aux-steps` and `--cpu-baseline` apply.
+
+`--dump-outputs DIR` writes what the last timed step handed back, as float32 DIR/<name>.npy
+(rank 0, copied before any replay touches the state): `grads` (the all-reduced packed gradient
+[centers 3M | colors 3M | radius M | light 3 | ambient 1]), `loss` (the loss sum), `params_raw`
+and `params_activated` (the parameters after the step's optimizer update), `adam_m`, `adam_v`.
+The scenes, cameras and targets are seeded and every step is deterministic, so two runs with the
+same arguments start from identical inputs.
+
+Extra objects on the JSON line (--full):
   roofline      -- the dominant kernel (rm_ray_kernel<train>) timed with hipEvents from its own
                    dispatch packet inside the timed region (every 5th step, --timing-every);
                    algorithmic FLOP = 16*(S+10)*M per ray. `achieved`/`frac`
@@ -78,6 +93,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: train-kernel and per-step event "
+                         "times, the untimed replays (roofline, value_exit_off), per-rank times, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (gradient, loss, updated parameters, Adam "
+                         "moments) as float32 DIR/<name>.npy")
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--spheres", type=int, default=256)
@@ -150,6 +171,10 @@ def parse():
     ap.add_argument("--skip-escaped", choices=["on", "off"], default="off",
                     help="RM_MARCH_SKIP_ESCAPED: skip ray blocks that provably leave the scene (exact)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps takes at least 1, --warmup at least 0")
+    if not args.full:  # a plain run: the timed steps alone
+        args.kernel_timing, args.aux_steps, args.cpu_baseline = "off", 0, "off"
     if args.global_views is not None and args.views_per_gpu is not None:
         ap.error("--global-views (strong scaling) and --views-per-gpu (weak scaling) are exclusive")
     if args.global_views is None and args.views_per_gpu is None:
@@ -282,8 +307,12 @@ def main():
         print(f"error: --gpus {args.gpus} but WORLD_SIZE={world}", file=sys.stderr)
         sys.exit(2)
     if os.environ.get("RM_BENCH_RANK_PROBE") == "1":  # launcher test (CPU): report the rank layout, no GPU
-        print(json.dumps({"rank": rank, "local_rank": local, "world": world,
-                          "master": f"{os.environ.get('MASTER_ADDR')}:{os.environ.get('MASTER_PORT')}"}), flush=True)
+        # one write per line: the ranks share the launcher's stdout, and print() hands an unbuffered
+        # stream the text and the newline separately, so two ranks' lines could run together
+        sys.stdout.write(json.dumps({"rank": rank, "local_rank": local, "world": world,
+                                     "master": f"{os.environ.get('MASTER_ADDR')}:{os.environ.get('MASTER_PORT')}"})
+                         + "\n")
+        sys.stdout.flush()
         return
     json_out = _json_stdout()
 
@@ -464,8 +493,9 @@ def main():
     for i in range(args.warmup):
         step(i)
     # snapshot of the training state at the start of the timed region (for the untimed replays)
-    snap = (model.raw.clone(), model._act.clone(), opt.m.clone(), opt.v.clone(), opt.t,
-            None if model._col_h is None else model._col_h.clone(), None if sdev is None else sdev.clone())
+    snap = None if args.aux_steps <= 0 else (
+        model.raw.clone(), model._act.clone(), opt.m.clone(), opt.v.clone(), opt.t,
+        None if model._col_h is None else model._col_h.clone(), None if sdev is None else sdev.clone())
 
     def restore():
         model.raw.copy_(snap[0])
@@ -493,8 +523,8 @@ def main():
     every = max(args.timing_every, 1) if args.steps >= 4 * max(args.timing_every, 1) else 1
     # per-step events on the sampled steps only: an event record is a barrier packet on the stream
     # (~5 us of GPU idle each), which would inflate short steps (C2) if every step had two
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if j % every == 0 else None
-          for j in range(args.steps)]
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          if args.full and j % every == 0 else None for j in range(args.steps)]
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -519,6 +549,13 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    # what the last timed step handed back, copied before a replay touches the state
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        nm = rmm.packed_size(M)
+        outputs = {name: t.detach().float().cpu().numpy().copy() for name, t in (
+            ("grads", dp.buf[:nm]), ("loss", dp.buf[nm:]), ("params_raw", model.raw),
+            ("params_activated", model.activated_packed()), ("adam_m", opt.m), ("adam_v", opt.v))}
     ctx.timing(False)
     kern_ms, launches = ctx.collect_timing(reset=True)
     step_ms = torch.tensor([e[0].elapsed_time(e[1]) for e in ev if e is not None], dtype=torch.float64,
@@ -576,28 +613,31 @@ def main():
     ranks_info = None
     kern_rank_ms = kern_ms / max(timed_steps, 1)  # this rank's train-kernel time per step
     if dist is not None:
-        # per-rank train-kernel and all-reduce times (sampled steps), before the max over ranks
-        ar_ms = dp.collect_allreduce_ms()
-        # (RCCL gathers device tensors; the gloo rehearsal host tensors)
-        mine = torch.tensor([kern_rank_ms, ar_ms if ar_ms is not None else -1.0], dtype=torch.float64,
-                            device="cuda" if backend == "nccl" else "cpu")
-        every_rank = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(every_rank, mine)
-        per = torch.stack(every_rank).cpu().numpy()
-        ranks_info = {"train_kernel_ms_per_step": [round(float(x), 4) for x in per[:, 0]],
-                      "train_kernel_ms_min_max": [round(float(per[:, 0].min()), 4), round(float(per[:, 0].max()), 4)],
-                      "allreduce_ms_per_step": [round(float(x), 4) for x in per[:, 1]],
-                      "allreduce_ms_min_max": [round(float(per[:, 1].min()), 4), round(float(per[:, 1].max()), 4)],
-                      "allreduce_note": "hipEvents on the compute stream around dist.all_reduce of the 7M+5-float "
-                                        "[gradient | loss] on every timed step the kernel is timed on: the collective "
-                                        "plus the wait for the slowest rank's train step",
-                      "allreduce_bytes": 4 * (rmm.packed_size(M) + 1)}
+        if args.full:
+            # per-rank train-kernel and all-reduce times (sampled steps), before the max over ranks
+            ar_ms = dp.collect_allreduce_ms()
+            # (RCCL gathers device tensors; the gloo rehearsal host tensors)
+            mine = torch.tensor([kern_rank_ms, ar_ms if ar_ms is not None else -1.0], dtype=torch.float64,
+                                device="cuda" if backend == "nccl" else "cpu")
+            every_rank = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(every_rank, mine)
+            per = torch.stack(every_rank).cpu().numpy()
+            ranks_info = {"train_kernel_ms_per_step": [round(float(x), 4) for x in per[:, 0]],
+                          "train_kernel_ms_min_max": [round(float(per[:, 0].min()), 4),
+                                                      round(float(per[:, 0].max()), 4)],
+                          "allreduce_ms_per_step": [round(float(x), 4) for x in per[:, 1]],
+                          "allreduce_ms_min_max": [round(float(per[:, 1].min()), 4), round(float(per[:, 1].max()), 4)],
+                          "allreduce_note": "hipEvents on the compute stream around dist.all_reduce of the 7M+5-float "
+                                            "[gradient | loss] on every timed step the kernel is timed on: the "
+                                            "collective plus the wait for the slowest rank's train step",
+                          "allreduce_bytes": 4 * (rmm.packed_size(M) + 1)}
         t = torch.tensor([elapsed, kern_ms, canon_ms or 0.0, exit_off_s or 0.0], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms, canon_ms, exit_off_s = float(t[0]), float(t[1]), (float(t[2]) or None), (float(t[3]) or None)
-        dist.all_reduce(step_ms, op=dist.ReduceOp.MAX)
+        if args.full:
+            dist.all_reduce(step_ms, op=dist.ReduceOp.MAX)
     step_ms = step_ms.cpu().numpy()
-    med_ms = float(np.median(step_ms))
+    med_ms = float(np.median(step_ms)) if step_ms.size else None  # per-step events: --full
 
     blocks_run, blocks_skipped = st["blocks"], st["blocks_skipped"]
     skipped_frac = blocks_skipped / max(blocks_run, 1)
@@ -718,6 +758,10 @@ def main():
     if rank == 0 and world == 1 and args.cpu_baseline == "auto":
         cpu = cpu_baseline(args, sc0, sc1, cams[0], W, H, M, S, K)
 
+    if outputs is not None:  # rank 0, --dump-outputs
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     if rank == 0:
         line = {
             "metric": METRIC,
@@ -726,6 +770,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
@@ -753,13 +798,14 @@ def main():
                                        if args.as_rank is None else
                                        f"rank {args.as_rank[0]} of views-dp{args.as_rank[1]}, alone on one GPU "
                                        f"(no all-reduce)")},
-            "value_median": round(rays_global / (med_ms * 1e-3) / 1e6, 3),
+            "value_median": None if med_ms is None else round(rays_global / (med_ms * 1e-3) / 1e6, 3),
             "value_exit_off": None if not exit_off_s else round(rays_global * args.steps / exit_off_s / 1e6, 3),
             "value_exit_off_note": "the same steps replayed untimed-by-events with the exact early exit off (every "
                                    "ray does the full march): whole-step Mrays/s independent of how many rays escape",
-            "ms_per_step_median": round(med_ms, 4),
+            "ms_per_step_median": None if med_ms is None else round(med_ms, 4),
             "host_submit_ms_per_step": round(host_s / args.steps * 1e3, 4),
-            "ms_per_step_min_max": [round(float(step_ms.min()), 4), round(float(step_ms.max()), 4)],
+            "ms_per_step_min_max": (None if med_ms is None else
+                                    [round(float(step_ms.min()), 4), round(float(step_ms.max()), 4)]),
             "roofline": roofline,
             "ranks": ranks_info,
             "cpu_baseline": cpu,

@@ -25,7 +25,7 @@ def _bench(*args):
 
 
 def test_bench_json_contract():
-    d = _bench("--steps", "4", "--warmup", "1", "--width", "128", "--height", "128", "--views-per-gpu", "2",
+    d = _bench("--full", "--steps", "4", "--warmup", "1", "--width", "128", "--height", "128", "--views-per-gpu", "2",
                "--cpu-sample", "2048", "--cpu-seconds", "0.2")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -51,9 +51,33 @@ def test_bench_json_contract():
 
 
 def test_bench_without_kernel_timing():
-    d = _bench("--steps", "2", "--warmup", "1", "--width", "64", "--height", "64", "--views-per-gpu", "1",
+    d = _bench("--full", "--steps", "2", "--warmup", "1", "--width", "64", "--height", "64", "--views-per-gpu", "1",
                "--cpu-baseline", "off", "--kernel-timing", "off")
     assert d["value"] > 0 and d["roofline"] is None and d["cpu_baseline"] is None
+
+
+def test_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times the steps alone -- no roofline, no CPU baseline, no per-step
+    events -- and --dump-outputs saves what the last timed step computed as float32 .npy; a second
+    run with the same arguments starts from the same inputs and writes the same arrays."""
+    import numpy as np
+    common = ("--steps", "3", "--warmup", "1", "--width", "64", "--height", "64", "--views-per-gpu", "2",
+              "--spheres", "40")
+    lines = [_bench(*common, "--dump-outputs", str(tmp_path / name)) for name in ("a", "b")]
+    npar = 7 * 40 + 4
+    for d in lines:
+        assert d["steps"] == 3 and d["full"] is False and d["value"] > 0 and d["finite"]
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["ms_per_step_median"] is None
+        assert abs(d["value"] - 2 * 64 * 64 / (d["ms_per_step"] * 1e-3) / 1e6) <= 0.01 * d["value"]
+    shapes = {"grads": npar, "loss": 1, "params_raw": npar, "params_activated": npar, "adam_m": npar, "adam_v": npar}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in shapes)
+    for name, n in shapes.items():
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype == np.float32 and a.shape == (n,) and np.isfinite(a).all(), name
+        assert np.array_equal(a, b), name
+    g = np.load(tmp_path / "a" / "grads.npy")
+    assert np.abs(g).max() > 0 and np.load(tmp_path / "a" / "loss.npy")[0] > 0
+    assert np.abs(np.load(tmp_path / "a" / "adam_v.npy")).max() > 0  # the optimizer ran on that gradient
 
 
 def test_graph_refuses_rotating_views():
@@ -69,7 +93,7 @@ def test_bench_annealed_k_and_rank_share():
     """--anneal-k K0 (train.rs:174's schedule over the timed steps) is named in the workload and the
     config; --as-rank R/N runs rank R's fixed share of an N-rank strong step alone (its views, its
     rays in value); the backward sweeps' ray shares are reported and bounded."""
-    d = _bench("--steps", "3", "--warmup", "1", "--width", "64", "--height", "64", "--global-views", "4",
+    d = _bench("--full", "--steps", "3", "--warmup", "1", "--width", "64", "--height", "64", "--global-views", "4",
                "--ring", "4", "--anneal-k", "5", "--cpu-baseline", "off")
     assert d["config"]["anneal_k_from"] == 5.0 and "k annealed 5->32" in d["config"]["workload"]
     bw = d["roofline"]["backward_rays_frac"]

@@ -20,8 +20,8 @@ pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="n
 def test_bench_two_ranks_gloo_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["RM_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-                        "--views-per-gpu", "2", "--cpu-baseline", "off", "--aux-steps", "0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4",
+                        "--warmup", "1", "--views-per-gpu", "2", "--cpu-baseline", "off", "--aux-steps", "0"],
                        env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -52,7 +52,7 @@ benchab)
   for r in $(seq $N); do
     for v in tree $V; do
       use $v || exit 1
-      timeout -k 10 300 python bench.py --cpu-baseline off "$@" > $O/${C}_${v}_$r.json 2> $O/${C}_${v}_$r.err \
+      timeout -k 10 300 python bench.py --full --cpu-baseline off "$@" > $O/${C}_${v}_$r.json 2> $O/${C}_${v}_$r.err \
         || { tail $O/${C}_${v}_$r.err; exit 1; }
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[2], sys.argv[3], d['value'], d['ms_per_step'], r['kernel_ms_per_step'], r['frac'], r['executed_frac'])" \
         $O/${C}_${v}_$r.json $C $v
@@ -68,7 +68,7 @@ envab)
     for e in "${ENVS[@]}"; do
       tagv=$(echo "$e" | tr -c 'A-Za-z0-9_\n' '_')
       if [ "$e" = - ]; then e="RM_NOOP=1"; fi
-      env $e timeout -k 10 300 python bench.py --cpu-baseline off $ARGS > $O/${C}_${tagv}_$r.json 2> $O/${C}_${tagv}_$r.err \
+      env $e timeout -k 10 300 python bench.py --full --cpu-baseline off $ARGS > $O/${C}_${tagv}_$r.json 2> $O/${C}_${tagv}_$r.err \
         || { tail $O/${C}_${tagv}_$r.err; exit 1; }
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(sys.argv[2], sys.argv[3], d['value'], d['ms_per_step'], r['kernel_ms_per_step'], r['frac'], r['executed_frac'])" \
         $O/${C}_${tagv}_$r.json $C "$e"

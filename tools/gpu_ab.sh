@@ -40,6 +40,7 @@ for r in $(seq 1 $ROUNDS); do
         c5s) args="--width 64 --height 64 --spheres 4096 --march-steps 128 --views-per-gpu 1 --steps 4 --warmup 2" ;;
         c5g) args="--march-steps 128 --views-per-gpu 1 --steps 6 --warmup 2 --color-dtype f16 --cameras tests/golden/cameras.json --targets dango --scene-json profiles/r05a_grown_scene_4096.json" ;;
       esac
+      args="--full $args"  # the lines below read roofline.* (kernel time, executed work)
       env $envs timeout -k 10 200 python bench.py --cpu-baseline off $args $extra > gpurun_out/ab/${c}_v${i}_$r.json \
         2> gpurun_out/ab/${c}_v${i}_$r.err || { tail -5 gpurun_out/ab/${c}_v${i}_$r.err; exit 1; }
       # a variant whose executed work differs from the first variant's did other work (e.g. trained

@@ -22,7 +22,7 @@ mkdir -p $O
 run() {
   name=$1; key=$2; shift 2
   if [ -n "$ONLY" ] && [[ " $ONLY " != *" $name "* ]]; then return 0; fi
-  timeout -k 10 300 python bench.py --cpu-baseline off "$@" > $O/$name.json 2> $O/$name.err || return $?
+  timeout -k 10 300 python bench.py --full --cpu-baseline off "$@" > $O/$name.json 2> $O/$name.err || return $?
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/prof_$name -o run -- python3 bench.py --cpu-baseline off --aux-steps 0 "$@" > $O/prof_$name.log 2>&1 || return $?
   if [ -n "$PMC" ]; then
     local PB="python3 bench.py --cpu-baseline off --aux-steps 0 --steps 3 --warmup 1 $*"
@@ -31,7 +31,7 @@ run() {
     timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_MFMA SQ_WAVES --kernel-trace --output-format csv -d $R/$O/pmc_${name}_sq1 -o run -- $PB >> $O/pmc_$name.log 2>&1 && \
     timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $R/$O/pmc_${name}_sq2 -o run -- $PB >> $O/pmc_$name.log 2>&1 && \
     RM_NO_EARLY_EXIT=1 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_MFMA SQ_WAVES --kernel-trace --output-format csv -d $R/$O/pmc_${name}_sq1x -o run -- $PB >> $O/pmc_$name.log 2>&1 && \
-    timeout -k 10 300 python3 bench.py --cpu-baseline off --steps 3 --warmup 1 "$@" > $O/${name}_pmcargs.json && \
+    timeout -k 10 300 python3 bench.py --full --cpu-baseline off --steps 3 --warmup 1 "$@" > $O/${name}_pmcargs.json && \
     python3 tools/pmc_summary.py $O/pmc_${name}_fetch $O/pmc_${name}_write profiles/${TAG}_pmc_traffic.json $key auto $CALIB && \
     python3 tools/pmc_sq_summary.py profiles/${TAG}_pmc_sq.json $key $O/pmc_${name}_sq1 $O/pmc_${name}_sq2 $O/pmc_${name}_sq1x $O/${name}_pmcargs.json || return 1
   fi

@@ -29,7 +29,7 @@ for step in "$@"; do
           || { tail $O/small.err; exit 1; }
       done ;;
     bench)
-      timeout -k 10 300 python bench.py > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+      timeout -k 10 300 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
       cat $O/bench.json ;;
     train)
       mkdir -p $O/train_out

@@ -16,6 +16,8 @@ against it:
     python tools/predict_scaling.py --bench profiles/r05_bench.json --balance profiles/r04b_shard_balance.json \
         --allreduce profiles/r05b_allreduce.json [--hop-us 2.5] [--slices 2=... 4=... 8=...] \
         > profiles/r05_scaling_prediction.json
+Every bench line read here comes from `bench.py --full` (the roofline object: train-kernel time per
+step and per launch, executed fraction).
 With --per-call the N = 1 step is run as N calls of 80/N views (bench.py --views-per-call 80/N):
 each call's launch is what one rank's launch is at N ranks, on the same (all-reduced) trajectory;
 T(N) = one call's train kernel x (slowest / mean slice) + one call's share of the step's other
