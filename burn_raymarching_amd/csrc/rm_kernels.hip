@@ -3794,6 +3794,7 @@ __global__ void rm_sum_small(const float* __restrict__ parts, int n, float* __re
 }
 
 #include "rm_small.h"
+#include "rm_raygrad.h"
 
 // rm_debug_stall: one wave that holds its stream until the host sets *flag (a system-scope load
 // of host-mapped memory, polled with s_sleep) or max_ticks of the 100 MHz real-time counter have
@@ -3818,6 +3819,8 @@ struct rm_context {
   std::string err;
   void* ws = nullptr;  // partials | segment sums | small scratch
   size_t ws_bytes = 0;
+  float* rg_ws = nullptr;  // ray-gradient calls: march t [rays] | per-view partial rows (rm_raygrad_kernel)
+  size_t rg_bytes = 0;
   bool timing = false;  // record hipEvents around every per-ray kernel launch
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
@@ -4014,6 +4017,29 @@ int ensure_ws(rm_context* ctx, size_t bytes) {
     return fail(ctx, RM_ERR_OOM, "workspace allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
   }
   ctx->ws_bytes = bytes;
+  return RM_OK;
+}
+
+// Workspace of the ray-gradient calls (rm_render_diff_backward_rays / _cameras): the replayed
+// march's t for every ray, then one partial row per 256-ray block of every view.
+size_t rg_need(long long rays) {
+  const long long rows = (rays + kBlock - 1) / kBlock + RM_MAX_VIEWS_PER_CALL;
+  return (size_t)(rays + rows * kRgCols + 64) * sizeof(float);
+}
+
+int ensure_rg(rm_context* ctx, size_t bytes) {
+  if (ctx->rg_bytes >= bytes) return RM_OK;
+  if (ctx->rg_ws) {
+    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RM_HIP(ctx, hipFree(ctx->rg_ws));
+    ctx->rg_ws = nullptr;
+    ctx->rg_bytes = 0;
+  }
+  if (hipMalloc(&ctx->rg_ws, bytes) != hipSuccess) {
+    ctx->rg_ws = nullptr;
+    return fail(ctx, RM_ERR_OOM, "ray-gradient workspace allocation of %zu bytes failed", bytes);
+  }
+  ctx->rg_bytes = bytes;
   return RM_OK;
 }
 
@@ -4917,6 +4943,10 @@ void rm_destroy(rm_context* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipFree(ctx->ws);
   }
+  if (ctx->rg_ws) {
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipFree(ctx->rg_ws);
+  }
   delete ctx;
 }
 
@@ -4951,6 +4981,8 @@ int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres) {
     RM_HIP(ctx, hipMemsetAsync(ctx->opt_arrival, 0, 128, ctx->stream));
   }
   if (!ctx->opt_pre) RM_HIP(ctx, hipMalloc(&ctx->opt_pre, sizeof(float) * (4 * kOptPreStride + 2)));
+  int rc;
+  if ((rc = ensure_rg(ctx, rg_need(std::max<int64_t>(max_rays, 1)))) != RM_OK) return rc;
   return ensure_ws(ctx, ws_need(std::max<int64_t>(max_rays, 1), max_spheres));
 }
 
@@ -5539,6 +5571,213 @@ int rm_train_iteration(rm_context* ctx, const float* ray_org, const float* ray_d
     return rc;
   return rm_optimizer_step(ctx, raw_packed, grad_packed, adam_m, adam_v, M, step, lr, weight_decay, with_penalties,
                            loss_penalty, act_packed);
+}
+
+}  // extern "C"
+
+// ---- ray and camera-pose gradients (rm_raygrad.h) -------------------------------------------
+namespace {
+
+struct RayGradCall {
+  bool cam = false;
+  const float* org = nullptr;
+  const float* dir = nullptr;
+  long long n = 0;
+  const rm_camera* cams = nullptr;
+  int views = 0, W = 0, H = 0;
+  const rm_scene* scene = nullptr;
+  const rm_march* march = nullptr;
+  const float* gout = nullptr;
+  const float* t_in = nullptr;
+  float* g_org = nullptr;
+  float* g_dir = nullptr;
+  rm_camera* grad_cams = nullptr;
+  int accumulate = 0;
+};
+
+int run_raygrad(rm_context* ctx, const RayGradCall& c) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  int rc;
+  if ((rc = check_scene(ctx, c.scene, true)) != RM_OK) return rc;
+  if ((rc = check_march(ctx, c.march)) != RM_OK) return rc;
+  if (c.cam) {
+    if (!c.cams) return fail(ctx, RM_ERR_INVALID_ARG, "cams is NULL");
+    if (c.views < 1 || c.views > RM_MAX_VIEWS_PER_CALL)
+      return fail(ctx, RM_ERR_INVALID_ARG, "num_views %d out of [1, %d]", c.views, RM_MAX_VIEWS_PER_CALL);
+    if (c.W < 1 || c.H < 1 || (long long)c.W * c.H > (1LL << 28))
+      return fail(ctx, RM_ERR_INVALID_ARG, "bad image size %dx%d", c.W, c.H);
+    if (!c.grad_cams) return fail(ctx, RM_ERR_INVALID_ARG, "grad_cams is NULL");
+  } else {
+    if (c.n < 0) return fail(ctx, RM_ERR_INVALID_ARG, "num_rays %lld < 0", c.n);
+    if (c.n > 0 && (!c.org || !c.dir)) return fail(ctx, RM_ERR_INVALID_ARG, "ray_org/ray_dir is NULL");
+    if (!c.g_org && !c.g_dir) return fail(ctx, RM_ERR_INVALID_ARG, "grad_org and grad_dir are both NULL");
+  }
+  const long long n = c.cam ? (long long)c.views * c.W * c.H : c.n;
+  if (n > 0 && !c.gout) return fail(ctx, RM_ERR_INVALID_ARG, "grad_out is NULL");
+  if (n == 0) return RM_OK;
+  const long long bpv = c.cam ? ((long long)c.W * c.H + kBlock - 1) / kBlock : 0;
+  if ((rc = ensure_rg(ctx, rg_need(n))) != RM_OK) return rc;
+
+  // no saved t: the existing forward replays the march into the workspace (escaped rays' t carries
+  // the documented guarantee); the gradient kernel itself never marches
+  const float* t_in = c.t_in;
+  if (!t_in) {
+    Call f;
+    f.mode = kFwd;
+    f.cam = c.cam;
+    f.org = c.org;
+    f.dir = c.dir;
+    f.n = c.n;
+    f.cams = c.cams;
+    f.views = c.views;
+    f.W = c.W;
+    f.H = c.H;
+    f.scene = c.scene;
+    f.march = c.march;
+    f.t_out = ctx->rg_ws;
+    if ((rc = run(ctx, f)) != RM_OK) return rc;
+    t_in = ctx->rg_ws;
+  }
+  ctx->opt_prepared = false;
+
+  const int M = c.scene->num_spheres, Mpad = pad_spheres(M);
+  KArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.org = c.org;
+  a.dir = c.dir;
+  a.centers = c.scene->centers;
+  if ((c.march->flags & RM_MARCH_COLOR_F16) != 0) a.colors_h = reinterpret_cast<const _Float16*>(c.scene->colors);
+  else a.colors = c.scene->colors;
+  a.radius = c.scene->radius;
+  a.light_dir = c.scene->light_dir;
+  a.ambient = c.scene->ambient;
+  a.M = M;
+  a.Mpad = Mpad;
+  a.steps = c.march->steps;
+  a.k = c.march->smooth_k;
+  a.eps = c.march->normal_eps;
+  a.csharp = c.march->color_sharpness;
+  a.msharp = c.march->mask_sharpness;
+  a.gout = c.gout;
+  a.t_in = t_in;
+  a.lse_slack = (float)(std::log((double)M) / (double)a.k * (1.0 + 1e-6)) + 1e-7f;
+  a.rec = rec_floats(Mpad);
+  RayGradCams tail;
+  if (c.cam) {
+    if (c.views <= kInlineCams) {
+      for (int v = 0; v < c.views; ++v)
+        if ((rc = make_basis(ctx, c.cams[v], c.W, c.H, a.cams[v])) != RM_OK) return rc;
+    } else {
+      Call u;
+      u.mode = kBwd;
+      u.cam = true;
+      u.cams = c.cams;
+      u.views = c.views;
+      u.W = c.W;
+      u.H = c.H;
+      if ((rc = upload_cams(ctx, u, a)) != RM_OK) return rc;
+    }
+    a.width = c.W;
+    a.height = c.H;
+    a.num_views = c.views;
+    a.tiling = (c.W % 16 == 0 && c.H % 16 == 0 && (c.march->flags & RM_MARCH_ROW_ORDER) == 0) ? 2 : 0;
+    std::memset(&tail, 0, sizeof tail);
+    for (int v = 0; v < c.views; ++v) tail.c[v] = c.cams[v];
+  }
+  // sphere records of this call (rm_prep_kernel; fp16 colours are widened there)
+  {
+    const int np = Mpad / 2, nprep = (np + 255) / 256;
+    const size_t need = rec_bytes(np, nprep);
+    if (need > ctx->rec_bytes) {
+      if (ctx->rec) {
+        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RM_HIP(ctx, hipFree(ctx->rec));
+        ctx->rec = nullptr;
+        ctx->rec_bytes = 0;
+      }
+      if (hipMalloc(&ctx->rec, need) != hipSuccess) return fail(ctx, RM_ERR_OOM, "record buffer (%zu B)", need);
+      ctx->rec_bytes = need;
+    }
+    hipLaunchKernelGGL(rm_prep_kernel, dim3(nprep), dim3(256), 0, ctx->stream, a, (float4*)ctx->rec);
+    RM_HIP(ctx, hipGetLastError());
+    if (nprep > 1) {
+      float* hdr = reinterpret_cast<float*>((char*)ctx->rec + (size_t)np * (7 * 16 + 8));
+      float* esc = reinterpret_cast<float*>((char*)ctx->rec + esc_offset(np, nprep));
+      hipLaunchKernelGGL(rm_prep_finish, dim3(1), dim3(256), 0, ctx->stream, a, hdr, esc, nprep);
+      RM_HIP(ctx, hipGetLastError());
+    }
+    a.rec_buf = (const float4*)ctx->rec;
+  }
+  RayGradArgs r{};
+  r.g_org = c.g_org;
+  r.g_dir = c.g_dir;
+  r.accumulate = c.accumulate ? 1 : 0;
+  hipEvent_t ev0, ev1;
+  if (c.cam) {
+    // the partial rows follow the t of all n rays (the replayed march may live there)
+    r.partial = ctx->rg_ws + n;
+    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
+    hipExtLaunchKernelGGL((rm_raygrad_kernel<true>), dim3((unsigned)bpv, (unsigned)c.views), dim3(kBlock), 0,
+                          ctx->stream, ev0, ev1, 0u, a, r);
+    RM_HIP(ctx, hipGetLastError());
+    hipLaunchKernelGGL(rm_raygrad_finish, dim3((unsigned)c.views), dim3(256), 0, ctx->stream, r.partial, (int)bpv, tail,
+                       reinterpret_cast<float*>(c.grad_cams), r.accumulate);
+    RM_HIP(ctx, hipGetLastError());
+    return RM_OK;
+  }
+  for (long long done = 0; done < n;) {
+    const long long nb = std::min<long long>((n - done + kBlock - 1) / kBlock, max_blocks_per_launch());
+    const long long nr = std::min<long long>(n - done, nb * kBlock);
+    a.ray_begin = done;
+    a.n_rays = nr;
+    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
+    hipExtLaunchKernelGGL((rm_raygrad_kernel<false>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream, ev0, ev1, 0u,
+                          a, r);
+    RM_HIP(ctx, hipGetLastError());
+    done += nr;
+  }
+  return RM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rm_render_diff_backward_rays(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
+                                 const rm_scene* scene, const rm_march* march, const float* grad_out,
+                                 const float* t_march, float* grad_org, float* grad_dir, int32_t accumulate) {
+  RayGradCall c;
+  c.cam = false;
+  c.org = ray_org;
+  c.dir = ray_dir;
+  c.n = num_rays;
+  c.scene = scene;
+  c.march = march;
+  c.gout = grad_out;
+  c.t_in = t_march;
+  c.g_org = grad_org;
+  c.g_dir = grad_dir;
+  c.accumulate = accumulate;
+  return run_raygrad(ctx, c);
+}
+
+int rm_render_diff_backward_cameras(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width,
+                                    int32_t height, const rm_scene* scene, const rm_march* march,
+                                    const float* grad_out, const float* t_march, rm_camera* grad_cams,
+                                    int32_t accumulate) {
+  RayGradCall c;
+  c.cam = true;
+  c.cams = cams;
+  c.views = num_views;
+  c.W = width;
+  c.H = height;
+  c.scene = scene;
+  c.march = march;
+  c.gout = grad_out;
+  c.t_in = t_march;
+  c.grad_cams = grad_cams;
+  c.accumulate = accumulate;
+  return run_raygrad(ctx, c);
 }
 
 }  // extern "C"

@@ -77,6 +77,11 @@ SIGNATURES = {
     "rm_render_diff_backward_camera": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32,
                                                       ctypes.POINTER(RmScene), ctypes.POINTER(RmMarch), _P, _P,
                                                       ctypes.POINTER(RmGrads), _I32]),
+    "rm_render_diff_backward_rays": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(RmScene),
+                                                    ctypes.POINTER(RmMarch), _P, _P, _P, _P, _I32]),
+    "rm_render_diff_backward_cameras": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32,
+                                                       ctypes.POINTER(RmScene), ctypes.POINTER(RmMarch), _P, _P,
+                                                       _P, _I32]),
     "rm_train_step": (ctypes.c_int, [_P, _P, _P, _P, _I64, _F, _F, ctypes.POINTER(RmScene),
                                      ctypes.POINTER(RmMarch), ctypes.POINTER(RmGrads), _P, _P, _I32]),
     "rm_train_step_camera": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32, _P, _F, _F,

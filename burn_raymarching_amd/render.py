@@ -6,6 +6,9 @@ Names and argument meaning follow the reference:
     is the analytic burn-autodiff backward computed by rm_render_diff_backward);
   * ``render_diff_camera(cams, width, height, ...)`` -- the same with rays generated
     in-kernel as create_camera_rays (camera.rs:30-90) would;
+  * ``render_diff_cameras(eye, target, fov_deg, width, height, ...)`` -- the same as an autograd
+    function over the camera tensors too (pose refinement; rm_render_diff_backward_cameras), and
+    ``render_diff_backward_rays`` / ``render_diff_backward_cameras`` -- the ray / pose gradients;
   * ``train_step(...)`` -- forward + compute_loss reconstruction seed + backward fused;
   * ``create_camera_rays(width, height, eye, target, fov_deg)`` -- host ray
     generation (camera.rs:30-90, a host loop in the reference too).
@@ -138,6 +141,81 @@ def render_diff_backward(ray_org, ray_dir, scene: Scene, smooth_k, grad_out, ste
     return g
 
 
+def render_diff_backward_rays(ray_org, ray_dir, scene: Scene, smooth_k, grad_out, steps=40, *, t_march=None,
+                              want_org=True, want_dir=True, grad_org=None, grad_dir=None, accumulate=False,
+                              normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0, flags=0):
+    """(dL/d ray_org, dL/d ray_dir) of sum(out * grad_out), [N,3] each (None where not wanted).
+
+    This is the gradient of the reference's graph (renderer_diff.rs:6-91) with respect to its
+    first two arguments: the march distance t and the normal are detached there, so with
+    p_a = o + d t, t_f = t + D(p_a), p_f = o + d t_f the result is g_o = g_p + g_pa and
+    g_d = t_f g_p + t g_pa (g_p = dL/dp_f, g_pa = (g_p . d) grad D(p_a)). It is what burn-autodiff
+    returns for these inputs, not the derivative of the image through the march. grad_org /
+    grad_dir: existing [N,3] tensors to write (or, with accumulate, add) into."""
+    n = ray_org.shape[0]
+    ray_org = _f32(ray_org, (n, 3), "ray_org")
+    ray_dir = _f32(ray_dir, (n, 3), "ray_dir")
+    grad_out = _f32(grad_out, (n, 3), "grad_out")
+    if t_march is not None:
+        t_march = _f32(t_march, (n,), "t_march")
+    for name, g in (("grad_org", grad_org), ("grad_dir", grad_dir)):
+        if g is not None and (_f32(g, (n, 3), name).data_ptr() != g.data_ptr()):
+            raise ValueError(f"{name} must be contiguous")
+    if accumulate and ((want_org and grad_org is None) or (want_dir and grad_dir is None)):
+        raise ValueError("accumulate needs the tensors to add into")
+    go = (grad_org if grad_org is not None else torch.empty((n, 3), device=ray_org.device)) if want_org else None
+    gd = (grad_dir if grad_dir is not None else torch.empty((n, 3), device=ray_org.device)) if want_dir else None
+    ctx = context(ray_org.device)
+    march = native.march_params(steps, smooth_k, normal_eps, color_sharpness, mask_sharpness, flags=flags)
+    march = scene.march_for(march)
+    ctx.check(ctx._lib.rm_render_diff_backward_rays(ctx.handle, _ptr(ray_org), _ptr(ray_dir), n,
+                                                    ctypes.byref(scene.c_struct()), ctypes.byref(march),
+                                                    _ptr(grad_out), _ptr(t_march), _ptr(go), _ptr(gd),
+                                                    1 if accumulate else 0), "rm_render_diff_backward_rays")
+    return go, gd
+
+
+def render_diff_backward_cameras(cams, width, height, scene: Scene, smooth_k, grad_out, steps=40, *, t_march=None,
+                                 grad_cams=None, accumulate=False, flags=0):
+    """dL/d(eye, target, fov_deg) per view of sum(out * grad_out): a [V,7] tensor laid out as
+    rm_camera (eye 0:3, target 3:6, fov_deg 6). Any number of views (chunks of 128 per call).
+
+    The ray gradients of render_diff_backward_rays chained through create_camera_rays
+    (camera.rs:41-79): the reference graph's gradient (march detached, normal detached), not the
+    derivative of the image. It follows finite differences of the image for a rigid shift of the
+    camera (eye and target moved together; cosines of 0.89 to 0.99 were measured), but need not
+    for eye moved alone against a fixed target, where the translation and rotation parts nearly
+    cancel (one of three measured cases gave a cosine of -0.93)."""
+    cams = list(cams)
+    v = len(cams)
+    if v == 0:
+        raise ValueError("at least one camera is required")
+    npix = width * height
+    grad_out = _f32(grad_out, (v * npix, 3), "grad_out")
+    if t_march is not None:
+        t_march = _f32(t_march, (v * npix,), "t_march")
+    dev = scene.centers.device
+    if grad_cams is None:
+        if accumulate:
+            raise ValueError("accumulate needs the tensor to add into")
+        grad_cams = torch.empty((v, 7), device=dev)
+    elif _f32(grad_cams, (v, 7), "grad_cams").data_ptr() != grad_cams.data_ptr():
+        raise ValueError("grad_cams must be contiguous")
+    ctx = context(dev)
+    march = native.march_params(steps, smooth_k, flags=flags)
+    march = scene.march_for(march)
+    for i in range(0, v, native.RM_MAX_VIEWS_PER_CALL):
+        chunk = cams[i:i + native.RM_MAX_VIEWS_PER_CALL]
+        lo, hi = i * npix, (i + len(chunk)) * npix
+        tt = t_march[lo:hi] if t_march is not None else None
+        ctx.check(ctx._lib.rm_render_diff_backward_cameras(ctx.handle, native.cameras(chunk), len(chunk), width, height,
+                                                           ctypes.byref(scene.c_struct()), ctypes.byref(march),
+                                                           _ptr(grad_out[lo:hi]), _ptr(tt),
+                                                           _ptr(grad_cams[i:i + len(chunk)]), 1 if accumulate else 0),
+                  "rm_render_diff_backward_cameras")
+    return grad_cams
+
+
 class _RenderDiffFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps):
@@ -154,17 +232,89 @@ class _RenderDiffFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         ray_org, ray_dir, t = ctx.saved_tensors
-        g = render_diff_backward(ray_org, ray_dir, ctx.scene, ctx.smooth_k, grad_out.contiguous().float(),
-                                 ctx.steps, t_march=t)
-        return (None, None, g["centers"], g["colors"], g["radius"].reshape(ctx.radius_shape), g["light_dir"],
+        grad_out = grad_out.contiguous().float()
+        need = ctx.needs_input_grad
+        g_org = g_dir = None
+        if need[0] or need[1]:
+            g_org, g_dir = render_diff_backward_rays(ray_org, ray_dir, ctx.scene, ctx.smooth_k, grad_out, ctx.steps,
+                                                     t_march=t, want_org=need[0], want_dir=need[1])
+        if not any(need[2:7]):  # only the rays are differentiated: the parameter backward does not run
+            return (g_org, g_dir) + (None,) * 7
+        g = render_diff_backward(ray_org, ray_dir, ctx.scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t)
+        return (g_org, g_dir, g["centers"], g["colors"], g["radius"].reshape(ctx.radius_shape), g["light_dir"],
                 g["ambient"].reshape(ctx.ambient_shape), None, None)
 
 
 def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps=40):
-    """renderer_diff.rs:6-91 on the GPU. Differentiable w.r.t. centers, colors, radius,
-    light_dir, ambient (ray_org / ray_dir are detached inputs, as in the reference's data)."""
+    """renderer_diff.rs:6-91 on the GPU. Differentiable w.r.t. centers, colors, radius, light_dir,
+    ambient and, when they require grad, ray_org / ray_dir (see render_diff_backward_rays: the
+    reference graph's gradient -- march detached, normal detached -- not the derivative of the
+    image). A caller who differentiates only the scene runs the parameter backward alone."""
     return _RenderDiffFn.apply(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, float(smooth_k),
                                int(steps))
+
+
+class _RenderDiffCamerasFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, eye, target, fov_deg, width, height, centers, colors, radius, light_dir, ambient, smooth_k,
+                steps):
+        scene = Scene(centers.detach(), colors.detach(), radius.detach(), light_dir.detach(), ambient.detach())
+        e, tg, f = eye.detach().cpu().tolist(), target.detach().cpu().tolist(), fov_deg.detach().cpu().tolist()
+        cams = [(e[i], tg[i], f[i]) for i in range(len(f))]
+        out, t = render_diff_camera(cams, width, height, scene, smooth_k, steps, return_t=True)
+        ctx.save_for_backward(t)
+        ctx.cams = cams
+        ctx.size = (width, height)
+        ctx.scene = scene
+        ctx.smooth_k = smooth_k
+        ctx.steps = steps
+        ctx.radius_shape = radius.shape
+        ctx.ambient_shape = ambient.shape
+        ctx.cam_meta = (eye.device, eye.dtype, target.device, target.dtype, fov_deg.device, fov_deg.dtype,
+                        fov_deg.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (t,) = ctx.saved_tensors
+        grad_out = grad_out.contiguous().float()
+        need = ctx.needs_input_grad
+        w, h = ctx.size
+        g_eye = g_tgt = g_fov = None
+        if need[0] or need[1] or need[2]:
+            gc = render_diff_backward_cameras(ctx.cams, w, h, ctx.scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t)
+            ed, et, td, tt, fd, ft, fs = ctx.cam_meta
+            g_eye = gc[:, 0:3].to(device=ed, dtype=et) if need[0] else None
+            g_tgt = gc[:, 3:6].to(device=td, dtype=tt) if need[1] else None
+            g_fov = gc[:, 6].reshape(fs).to(device=fd, dtype=ft) if need[2] else None
+        gs = (None,) * 5
+        if any(need[5:10]):
+            g = None
+            v, npix = len(ctx.cams), w * h
+            for i in range(0, v, native.RM_MAX_VIEWS_PER_CALL):  # the parameter backward takes 128 views a call
+                j = min(i + native.RM_MAX_VIEWS_PER_CALL, v)
+                gi = render_diff_backward_camera(ctx.cams[i:j], w, h, ctx.scene, ctx.smooth_k,
+                                                 grad_out[i * npix:j * npix], ctx.steps, t_march=t[i * npix:j * npix])
+                g = gi if g is None else {k: g[k] + gi[k] for k in g}
+            gs = (g["centers"], g["colors"], g["radius"].reshape(ctx.radius_shape), g["light_dir"],
+                  g["ambient"].reshape(ctx.ambient_shape))
+        return (g_eye, g_tgt, g_fov, None, None) + gs + (None, None)
+
+
+def render_diff_cameras(eye, target, fov_deg, width, height, centers, colors, radius, light_dir, ambient, smooth_k,
+                        steps=40):
+    """render_diff over the rays of create_camera_rays (camera.rs:30-90) for V cameras, differentiable
+    w.r.t. the camera tensors eye [V,3], target [V,3], fov_deg [V] and the scene: out [V*H*W, 3].
+
+    The camera tensors may live on the host or the device (the poses go to the kernels by value;
+    their gradients come back on the tensors' own device). The gradient is the reference graph's
+    (march detached, normal detached) chained through create_camera_rays, not the derivative of
+    the image: it follows finite differences for a rigid shift of the camera (eye and target moved
+    together; measured cosines 0.89 to 0.99) and so serves pose refinement of that kind, but it need
+    not for eye moved alone against a fixed target, where the translation and rotation parts
+    nearly cancel (one of three measured cases gave a cosine of -0.93)."""
+    return _RenderDiffCamerasFn.apply(eye, target, fov_deg, int(width), int(height), centers, colors, radius,
+                                      light_dir, ambient, float(smooth_k), int(steps))
 
 
 def render_diff_camera(cams, width, height, scene: Scene, smooth_k, steps=40, *, normal_eps=1e-4,

@@ -193,6 +193,28 @@ int rm_render_diff_backward_camera(rm_context* ctx, const rm_camera* cams, int32
                                    const float* grad_out, const float* t_march, const rm_grads* grads,
                                    int32_t accumulate);
 
+/* ---- backward w.r.t. the rays and the camera poses ------------------------- */
+/* The gradient of the reference's graph with respect to render_diff's first two arguments
+ * (renderer_diff.rs:6-15; the march t and the normal are detached, :25 and :41-46): with
+ * p_a = o + d t, t_f = t + D(p_a), p_f = o + d t_f, g_p = dL/dp_f and g_pa = (g_p . d) grad D(p_a),
+ *   dL/do = g_p + g_pa,   dL/dd = t_f g_p + t g_pa.
+ * It is the reference autodiff's gradient, not the derivative of the image through the march.
+ * Rays whose backward seeds are zero (every escaped ray) get exact zeros. One dedicated kernel
+ * (one ray per lane), no floating-point atomics; when t_march is NULL the forward replays the
+ * march first. RM_MARCH_COLOR_F16 is honoured; the march-path A/B flags apply to that replay only. */
+/* dL/d(ray_org), dL/d(ray_dir) of render_diff for grad_out = dL/d(out): [N,3] each, either NULL
+ * to skip it; accumulate != 0 adds. t_march as in rm_render_diff_backward. */
+int rm_render_diff_backward_rays(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
+                                 const rm_scene* scene, const rm_march* march, const float* grad_out,
+                                 const float* t_march, float* grad_org, float* grad_dir, int32_t accumulate);
+/* dL/d(eye, target, fov_deg) per view: grad_cams is DEVICE memory, num_views records laid out as
+ * rm_camera (7 floats). The ray gradients chained through create_camera_rays (camera.rs:41-79);
+ * math::normalize of a zero vector has a zero Jacobian here, so the result is finite. */
+int rm_render_diff_backward_cameras(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width,
+                                    int32_t height, const rm_scene* scene, const rm_march* march,
+                                    const float* grad_out, const float* t_march, rm_camera* grad_cams,
+                                    int32_t accumulate);
+
 /* ---- fused train step: forward + compute_loss seed + backward ------------- */
 /* The reconstruction term of compute_loss (training.rs:17-34): for each ray,
  * W = 10 where sum(target) > 0.01 else 1 + 4*progress, loss += sum_c |out-target|*W,
