@@ -21,7 +21,6 @@ constexpr int kBlock = RM_BLOCK;         // threads per block (256 = 4 waves)
 constexpr int kMinWavesPerSimd = RM_MIN_WAVES;  // register budget: 4 -> <= 128 VGPRs
 constexpr int kWaves = kBlock / 64;
 constexpr int kSphereAlign = 32;         // M is padded to a multiple of this
-constexpr int kChunkBwd = 32;            // spheres per backward partial-combine chunk
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kSafeRho = 4e-3f;        // rho >= this => max(q, 1e-6) is a no-op (q >= 1.6e-5)
 constexpr float kPadCenter = 1e15f;      // padding sphere center x: distance ~1e15 -> exp() underflows to 0

@@ -40,46 +40,6 @@
 #include "../../include/raymarch.h"
 #include "rm_device.h"
 
-#ifndef RM_PRIO_RAMP
-// s_setprio ramp over the march / post-march / backward phases: paid off when one launch filled
-// the GPU once (it evened out the co-resident waves' finish); with 10 views per launch and
-// partly-dead blocks backfilled it costs 4 % (1094 vs 1141 Mrays/s), so it is off by default.
-#define RM_PRIO_RAMP 0
-#endif
-#ifndef RM_BWD_TRANSPOSED
-#define RM_BWD_TRANSPOSED 1  // backward sweeps with one sphere per lane (0: one ray per lane)
-#endif
-#ifndef RM_BWD_PSQ_REG
-#define RM_BWD_PSQ_REG 0  // backward sweeps form |p|^2 from p in registers (1) or read it from LDS (0)
-#endif
-#ifndef RM_DEAD_EARLY
-// backward modes: a wave whose rays all escaped ends at the hand-off instead of waiting at its
-// barrier (A/B switch; measured equal, Appendix A of DESIGN.md)
-#define RM_DEAD_EARLY 0
-#endif
-#ifndef RM_MARCH_SCHED
-#define RM_MARCH_SCHED 1  // scheduling barriers in the matrix-core march loop (0: compiler's order)
-#endif
-#if RM_MARCH_SCHED
-#define RM_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#else
-#define RM_SCHED_BARRIER() ((void)0)
-#endif
-#ifndef RM_MARCH_BUFLOAD
-#define RM_MARCH_BUFLOAD 1  // matrix-core fragments by buffer loads (0: global loads)
-#endif
-#ifndef RM_MARCH_PK
-#define RM_MARCH_PK 1  // lse_mfma accumulates with v_pk_fma_f32 (two chains per ray; 0: one fma chain)
-#endif
-#ifndef RM_MFMA32
-#define RM_MFMA32 0  // the march's matrix-core tiles as v_mfma_f32_32x32x16_bf16 (32 spheres x 32 rays)
-#endif
-#ifndef RM_CYCLE_MAX
-#define RM_CYCLE_MAX 2  // longest period (2..4) the march's cycle exit detects (3, 4: no measurable gain)
-#endif
-#ifndef RM_HEAVY_PRIO
-#define RM_HEAVY_PRIO 0  // s_setprio(2) for the blocks of the RM_HEAVY_PRIO dearest cost classes
-#endif
 #ifndef RM_ORDER_CLASSES
 #define RM_ORDER_CLASSES 16  // cost classes of the cost-ordered dispatch (order_append)
 #endif
@@ -144,7 +104,6 @@ static_assert(kSplitWaves == 2 || kSplitWaves == 4, "split blocks have 2 or 4 wa
 constexpr int kSplitRays = RM_SPLIT_RAYS;
 static_assert(kSplitRays == 64 || kSplitRays == 32 || kSplitRays == 16, "split blocks hold 64, 32 or 16 rays");
 constexpr int kSplitCB = kSplitRays / 16;  // column blocks of 16 rays in the split march's tiles
-constexpr int kContClasses = 4;  // classes of the split continuation's block lists
 constexpr long long kSplitMaxRays = 262144;
 #ifndef RM_REDUCE_SEGS
 #define RM_REDUCE_SEGS 128
@@ -163,7 +122,7 @@ struct KArgs {
   float cull_min_d;  // scene distance at which the silhouette mask is exactly 0
   float lse_slack;  // ln(M) / k (rounded up): the hard min exceeds the soft-min by at most this
   unsigned long long* stats;  // nullable: [0] += 1 per escaped (skipped) block, [1] exited waves,
-                              // [2] march steps saved, [3] RM_LANE_STATS, [4] / [5] rays the two
+                              // [2] march steps saved, [3] unused (zero), [4] / [5] rays the two
                               // backward sweeps run for (non-zero seeds)
   float gone_d;               // > 0: rays that provably escape past this distance are `gone` (see the march)
   int early_exit;             // waves whose rays are all gone stop marching
@@ -213,36 +172,31 @@ struct KArgs {
   float* dbg;       // optional per-ray intermediates [n][16] (diagnostics; see rm_debug_intermediates)
   float* partials;  // [gridDim.x][rec], rec = Mpad*8 + 8
   long long rec;
-  // Continuation of a split launch (split_cont_steps, see run()): with cont_cap > 0 a block whose
-  // rays still march at step cont_cap saves its march state, appends its logical block to
-  // cont_list_w and ends; a launch with cont_resume = that step runs the saved blocks
-  // (cont_list[0..*cont_count)) from there (and may defer again at its own cont_cap). The lists
-  // are kContClasses class lists of cont_stride entries each, with kContClasses counts: a deferred
-  // block goes to the class of the march steps its slowest ray is predicted to need (the most
-  // first), and a continuation launch runs the classes in order -- the blocks likely to march to
-  // the end start first.
-  // cont_state: [7][cont_rays] per ray (t, lb, D_prev, t one and two steps back, gone, rho_lb) then
-  // [blocks][2] per block (choice history, steps saved).
+  // Continuation of a split launch (split_cont_caps, see run()). The split kernels march in ray
+  // mode: every march step takes the scene-uniform fixed shift (the running maximum where the
+  // scene does not admit it), so a ray's step is a function of its own state alone. A ray whose t
+  // repeats with period 2 retires with its final t by itself (the wave-level cycle exit
+  // generalised), and at a continuation cap the still-marching RAYS, not their groups, go on:
+  //  * first launch (cont_cap > 0, cont_resume = 0): a group whose rays still march at step
+  //    cont_cap saves every ray's state, appends itself to cont_list_w (*cont_count_w entries, in
+  //    arrival order) and its marching rays to ray_list_w (*ray_count_w entries), and ends;
+  //  * ray_cont launches (cont_resume = the cap before): a block marches kSplitRays listed rays
+  //    (ray_list[0..*ray_count), of any groups) from cont_resume to its own cont_cap, where it
+  //    lists the rays still marching again, or to the end, and writes their states back;
+  //  * resume launch (cont_resume = steps, ray_cont = 0): block b runs the post-march forward and
+  //    the backward of group cont_list[b], b < *cont_count, from the saved final states.
+  // The grouping of rays changes no bit (tests/test_gpu_split.py).
+  // cont_state: eight per-ray rows of cont_rays floats -- 0 t, 1 lb, 2 D_prev, 3 / 4 t one and two
+  // steps back, 5 the ray's code (0 marching, 1 gone, 2 retired), 6 rho_lb, 7 the ray's own choice
+  // history (as int bits) -- then, from float 8 cont_rays, two words per group: the group's choice
+  // history and its steps saved (as int bits).
   int cont_cap, cont_resume;
   float* cont_state;
   const int* cont_list;
   const int* cont_count;
   int* cont_list_w;
   int* cont_count_w;
-  int cont_stride;   // entries per class list
-  int cont_order;    // 0: every deferred block in class 0 (arrival order)
   long long cont_rays;
-  // Ray mode (split launches; RM_RAY_MODE): every march step takes the scene-uniform fixed shift
-  // (the running maximum where the scene does not admit it), so a ray's step is a function of its
-  // own state alone. Then a ray whose t repeats with period 2 retires with its final t by itself
-  // (the wave-level cycle exit generalised), and at a continuation cap the still-marching RAYS,
-  // not their groups, go on: the group saves every ray's state (cont_state gets an eighth per-ray
-  // row, the ray's choice history), appends itself to cont_list_w (class 0) and its marching rays
-  // to ray_list_w. A ray_cont launch marches 32 listed rays per block (ray_list[0..*ray_count),
-  // any groups) from cont_resume to its cap or to the end and writes their states back; the
-  // groups' post-march forward and backward then run in a resume launch (cont_resume = steps).
-  // The grouping of rays changes no bit.
-  int ray_mode;
   int ray_cont;
   const int* ray_list;
   const int* ray_count;
@@ -292,15 +246,7 @@ __host__ __device__ inline size_t tiles_offset(int npairs, int nprep) {
 }
 // Then the escape thresholds of the march: kEscTab floats (see write_bound).
 constexpr int kEscTab = 64;
-#ifdef RM_RAY_STATS
-constexpr int kStatsWords = 8;  // + [6] / [7]: lane-steps after the cap, run and compacted (measurement)
-#ifndef RM_RAY_STATS_CAP
-#define RM_RAY_STATS_CAP 16
-#endif
-#else
 constexpr int kStatsWords = 6;  // rm_stats device counters (KArgs::stats)
-#endif
-[[maybe_unused]] constexpr int kDeadCountSlot = 44;  // Lds::misc int: the hand-off's count of waves that ended early
 __host__ __device__ inline size_t esc_offset(int npairs, int nprep) {
   const size_t nrb = (size_t)npairs / 8;
   return tiles_offset(npairs, nprep) + nrb * 64 * 16 + nrb * 32 * sizeof(float);
@@ -320,7 +266,7 @@ struct Lds {  // the sphere records (global, scalar-loaded) plus the kernel's LD
   cf2_ptr P4;
   const uint4* At;  // lse_mfma sphere fragments (global)
   const float* Wt;  // lse_mfma weights (global)
-  float* slots;  // backward wave partials, 2 buffers (LDS); lse_mfma's ray exchange in the march
+  float* slots;  // LDS: the backward's ray images and shares; lse_mfma's ray exchange in the march
   float* misc;   // small LDS scratch
   __device__ __forceinline__ static float4 v4(f4v v) { return make_float4(v.x, v.y, v.z, v.w); }
   __device__ __forceinline__ float4 p0(int i) const { return v4(P0[i]); }
@@ -350,18 +296,16 @@ struct Lds {  // the sphere records (global, scalar-loaded) plus the kernel's LD
   }
 };
 
-// LDS: the backward's two partial buffers, or (during the march) lse_mfma's per-wave ray
+// LDS: the backward's ray images and g_t shares, or (during the march) lse_mfma's per-wave ray
 // exchange (64 x (16 + 16 + 4) B per wave); then 256 B of misc scratch.
-// The transposed backward (RM_BWD_TRANSPOSED) uses 15 x 64 ray-data floats (field-major) per wave
+// The backward (one sphere per lane) uses 15 x 64 ray-data floats (field-major) per wave
 // and kWaves x 64 g_t shares per wave (19.3 KB). The LDS of a block decides how many blocks a CU
 // holds once waves leave the march early (their registers free up, the block's LDS stays until its
 // last wave ends): 19.3 KB -> 8 blocks per CU (24.3 KB -> 6, 32.3 KB -> 4).
 constexpr int kBwdFields = 15;  // ray-image fields of the transposed backward
 constexpr size_t kSlotBwdT = ((size_t)kWaves * 64 * kBwdFields + (size_t)kWaves * kWaves * 64) * sizeof(float);
-constexpr size_t kSlotBytes0 = (size_t)2 * kWaves * kChunkBwd * 8 * sizeof(float) > (size_t)kWaves * 64 * 36
-                                   ? (size_t)2 * kWaves * kChunkBwd * 8 * sizeof(float)
-                                   : (size_t)kWaves * 64 * 36;
-constexpr size_t kSlotBytes = RM_BWD_TRANSPOSED && kSlotBwdT > kSlotBytes0 ? kSlotBwdT : kSlotBytes0;
+constexpr size_t kSlotBytes = kSlotBwdT;
+static_assert((size_t)kWaves * 64 * 36 <= kSlotBytes, "the march's ray exchange fits the slots");
 __host__ __device__ constexpr size_t lds_bytes() { return kSlotBytes + 256; }
 // the split march's two combine buffers (kWaves x 64 floats each) after the march exchange
 constexpr int kSplitCombOff = kWaves * 64 * 9;  // floats: xa, xb (64 uint4 per wave each), xs
@@ -486,29 +430,15 @@ __device__ __forceinline__ uint4 mfma_a_slice(const KArgs& a, int j, int g) {
   return make_uint4(pack2(z[0], z[1]), pack2(kBf16One, kBf16One), pack2(kBf16One, C[0]), pack2(C[1], C[2]));
 }
 // Element e of the tile array: v_mfma_f32_16x16x32_bf16 -- row block rb = e / 64 of 16 spheres,
-// lane l = e % 64 holds sphere 16 rb + (l & 15), slice l >> 4; RM_MFMA32 (v_mfma_f32_32x32x16_bf16,
-// two per 32 spheres: K halves m = 0, 1) -- block e / 128 of 32 spheres, m = (e / 64) & 1, lane l
-// holds sphere 32 rb + (l & 31), slice 2 m + (l >> 5). The same bytes per sphere either way.
+// lane l = e % 64 holds sphere 16 rb + (l & 15), slice l >> 4.
 __device__ __forceinline__ uint4 mfma_a_frag(const KArgs& a, int e) {
   const int l = e & 63;
-#if RM_MFMA32
-  return mfma_a_slice(a, 32 * (e >> 7) + (l & 31), 2 * ((e >> 6) & 1) + (l >> 5));
-#else
   return mfma_a_slice(a, 16 * (e >> 6) + (l & 15), l >> 4);
-#endif
 }
 // Sphere of weight slot e (per 16 spheres 32 slots: 16 unshifted | 16 fixed-shift weights in sphere
-// order; RM_MFMA32: per 32 spheres 64 slots, 32 | 32, slot h * 16 + 4 i + v of a half is sphere
-// 8 i + 4 h + v of the block -- the 32x32 result rows of lane half h)
-__device__ __forceinline__ int mfma_w_sphere(int e) {
-#if RM_MFMA32
-  const int x = e & 31;
-  return 32 * (e >> 6) + 8 * ((x >> 2) & 3) + 4 * (x >> 4) + (x & 3);
-#else
-  return 16 * (e >> 5) + (e & 15);
-#endif
-}
-__device__ __forceinline__ bool mfma_w_fixed(int e) { return (e & (RM_MFMA32 ? 32 : 16)) != 0; }
+// order)
+__device__ __forceinline__ int mfma_w_sphere(int e) { return 16 * (e >> 5) + (e & 15); }
+__device__ __forceinline__ bool mfma_w_fixed(int e) { return (e & 16) != 0; }
 
 // hdr[4..7] = the bounding sphere (c, R) of scene_bound, for the march's escape test, and its
 // distance thresholds T(n), n < kEscTab: a receding ray at distance d from c with n march steps
@@ -646,18 +576,14 @@ __global__ __launch_bounds__(256) void rm_prep_kernel(const KArgs a0, float4* __
   char* tiles = reinterpret_cast<char*>(rec) + tiles_offset(np, gridDim.x);
   uint4* At = reinterpret_cast<uint4*>(tiles);
   float* Wt = reinterpret_cast<float*>(At + (size_t)nrb * 64);
-#ifndef RM_DBG_NO_TILES
   for (int e = blockIdx.x * nt + threadIdx.x; e < nrb * 64; e += gridDim.x * nt) At[e] = mfma_a_frag(a, e);
-#endif
   for (int e = blockIdx.x * nt + threadIdx.x; e < nrb * 32; e += gridDim.x * nt) {
     const int j = mfma_w_sphere(e);
     const float krj = j < a.M ? kappa * a.radius[j] : 0.0f;
     Wt[e] = j >= a.M ? 0.0f : (mfma_w_fixed(e) ? fexp2(krj - kr_first) : fexp2(krj));
   }
   header_reduce(rmin, rmax, spread, gridDim.x == 1 ? hdr : hdr + (size_t)(1 + blockIdx.x) * kRecHeader);
-#ifndef RM_DBG_NO_BOUND
   if (gridDim.x == 1) write_bound(a, hdr, reinterpret_cast<float*>(reinterpret_cast<char*>(rec) + esc_offset(np, 1)));
-#endif
 }
 
 __global__ __launch_bounds__(256) void rm_prep_finish(const KArgs a, float* __restrict__ hdr, float* __restrict__ esc,
@@ -828,7 +754,7 @@ __device__ __forceinline__ void lse_point(const float p[3], const Lds& L, int np
 // lane l the ray of lane l mod 16 NCB; only the first NCB column blocks are multiplied and summed,
 // and the reduction takes the missing blocks as copies of the present ones. A ray's sum is the
 // same chain of the same terms as with NCB = 4 (the same bits; IEEE addition is commutative).
-template <bool CLAMP, bool FIXED, bool BUF = (RM_MARCH_BUFLOAD != 0), int NCB = 4>
+template <bool CLAMP, bool FIXED, int NCB = 4>
 __device__ __forceinline__ float lse_mfma(const float p[3], float k2, float sh, const uint4* __restrict__ At,
                                           const float* __restrict__ Wt, int nrb, uint4* xa, uint4* xb, float* xs,
                                           int lane) {
@@ -863,37 +789,31 @@ __device__ __forceinline__ float lse_mfma(const float p[3], float k2, float sh, 
     __builtin_amdgcn_wave_barrier();
     return 0.0f;
   }
-  // BUF: buffer loads -- the row block's byte offset in a scalar register, the lane's offset
-  // fixed in a vector register, no per-load 64-bit address arithmetic on the vector units (the
-  // unsplit march +3 %, the split march +2 % once its quarter bounds are scalar); else global loads
+  // buffer loads: the row block's byte offset in a scalar register, the lane's offset fixed in a
+  // vector register, no per-load 64-bit address arithmetic on the vector units (against global
+  // loads the unsplit march +3 %, the split march +2 % once its quarter bounds are scalar)
   const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)At, (short)0, 0x7fffffff, 0x00020000);
   const __amdgpu_buffer_rsrc_t rw =
       __builtin_amdgcn_make_buffer_rsrc((void*)(Wt + (FIXED ? 16 : 0)), (short)0, 0x7fffffff, 0x00020000);
   const int va = lane * 16, vw = g * 16;
-  const float* wsrc = Wt + (FIXED ? 16 : 0) + 4 * g;
   auto load_a = [&](int rb) {
-    if constexpr (BUF) return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, va, rb * 1024, 0));
-    else return __builtin_bit_cast(bf16x8, At[rb * 64 + lane]);
+    return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, va, rb * 1024, 0));
   };
   auto load_w = [&](int rb) {
-    if constexpr (BUF) return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rw, vw, rb * 128, 0));
-    else return *reinterpret_cast<const float4*>(wsrc + rb * 32);
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rw, vw, rb * 128, 0));
   };
   auto tile = [&](const bf16x8& A, f32x4 (&D)[NCB]) {
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) D[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B[cb], zero, 0, 0, 0);
   };
-#if RM_MARCH_PK  // packed accumulate: two chains per ray (v even / odd), one v_pk_fma_f32 per two terms
   f2 acc2[NCB];
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) acc2[cb] = sp(0.0f);
-#endif
   auto consume = [&](const f32x4 (&D)[NCB], const float4& w) {
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
       float q[4] = {D[cb].x, D[cb].y, D[cb].z, D[cb].w};
       const float wv[4] = {w.x, w.y, w.z, w.w};
-#if RM_MARCH_PK
       float rho[4];
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
@@ -906,14 +826,6 @@ __device__ __forceinline__ float lse_mfma(const float p[3], float k2, float sh, 
         const f2 x = FIXED ? sp(S[cb]) - f2{rho[v], rho[v + 1]} : f2{-rho[v], -rho[v + 1]};
         acc2[cb] = fma2(f2{wv[v], wv[v + 1]}, f2{fexp2(x.x), fexp2(x.y)}, acc2[cb]);
       }
-#else
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        if constexpr (CLAMP) q[v] = qclamp(q[v], QMIN);
-        const float rho = fsqrt(q[v]);
-        acc[cb] = fmaf(wv[v], fexp2(FIXED ? S[cb] - rho : -rho), acc[cb]);
-      }
-#endif
     }
   };
   // one tile at a time (registers: the march must not spill at 128 VGPRs); the fragments of the
@@ -925,25 +837,23 @@ __device__ __forceinline__ float lse_mfma(const float p[3], float k2, float sh, 
     tile(A, D);
     const bf16x8 A1 = load_a(rb + 1);
     const float4 w1 = load_w(rb + 1);
-    RM_SCHED_BARRIER();  // keep the loads a tile ahead of their use
+    __builtin_amdgcn_sched_barrier(0);  // keep the loads a tile ahead of their use
     consume(D, w);
-    RM_SCHED_BARRIER();
+    __builtin_amdgcn_sched_barrier(0);
     tile(A1, D);
     const int rn = min(rb + 2, nrb - 1);
     A = load_a(rn);
     w = load_w(rn);
-    RM_SCHED_BARRIER();
+    __builtin_amdgcn_sched_barrier(0);
     consume(D, w1);
-    RM_SCHED_BARRIER();
+    __builtin_amdgcn_sched_barrier(0);
   }
   // partial sums of ray 16cb + n sit in the four lane groups: one transposing reduction (two
   // v_permlane32_swap and one v_permlane16_swap, no LDS) leaves lane (n, g) with the total of
   // its own ray 16g + n: rows 0/2 keep the column blocks 0/2 summed over lane bit 5, rows 1/3
   // the blocks 1/3, then each row adds its bit-4 partner
-#if RM_MARCH_PK
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) acc[cb] = acc2[cb].x + acc2[cb].y;
-#endif
   // NCB < 4: column block cb + NCB is a copy of block cb (the lanes' rays repeat every 16 NCB)
 #pragma unroll
   for (int cb = NCB; cb < 4; ++cb) acc[cb] = acc[cb - NCB];
@@ -951,96 +861,6 @@ __device__ __forceinline__ float lse_mfma(const float p[3], float k2, float sh, 
   __builtin_amdgcn_wave_barrier();  // the exchange is rewritten by the next step
   return own;
 }
-
-#if RM_MFMA32
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-// lse_mfma with v_mfma_f32_32x32x16_bf16: per 32 spheres and 32 rays two MFMAs (K halves: slices
-// 0-1 with B = Sa, slices 2-3 with B = Sa / Sb by lane half), half the matrix-core instructions
-// of 16x16x32 per evaluation (each holds the SIMD's vector issue for 8 cycles). Lane (r, h) =
-// (l & 31, l >> 5) gets, per column block cb, 16 results of ray 32 cb + r: rows (i & 3) + 8 (i >> 2)
-// + 4 h (mfma_w_sphere's slot order); the two halves of a ray meet in one v_permlane32_swap.
-// Registers: one column block's tile at a time, the weights loaded as they are used, the ray side
-// re-read from the exchange (measured: Appendix A; 2 spilled VGPRs in the train kernel).
-template <bool CLAMP, bool FIXED, bool BUF = (RM_MARCH_BUFLOAD != 0)>
-__device__ __forceinline__ float lse_mfma32(const float p[3], float k2, float sh, const uint4* __restrict__ At,
-                                            const float* __restrict__ Wt, int nrb, uint4* xa, uint4* xb, float* xs,
-                                            int lane) {
-#pragma clang fp contract(off)
-  {
-    unsigned x[3], y[3], z[3], P[3];
-    split3(p[0], x[0], x[1], x[2]);
-    split3(p[1], y[0], y[1], y[2]);
-    split3(p[2], z[0], z[1], z[2]);
-    split3(k2 * psq(p), P[0], P[1], P[2]);
-    xa[lane] = make_uint4(pack2(x[0], x[1]), pack2(x[2], y[0]), pack2(y[1], y[2]), pack2(z[0], z[1]));
-    xb[lane] = make_uint4(pack2(z[2], z[2]), pack2(P[0], P[1]), pack2(P[2], kBf16One), pack2(kBf16One, kBf16One));
-    if constexpr (FIXED) xs[lane] = sh;
-  }
-  __builtin_amdgcn_wave_barrier();
-  const int r = lane & 31, h = lane >> 5;
-  float S[2];
-#pragma unroll
-  for (int cb = 0; cb < 2; ++cb) S[cb] = FIXED ? xs[32 * cb + r] : 0.0f;
-  const float QMIN = k2 * 1e-6f;
-  float acc[2] = {0.0f, 0.0f};
-  if (nrb == 0) {
-    __builtin_amdgcn_wave_barrier();
-    return 0.0f;
-  }
-  const int n32 = nrb >> 1;  // nrb (16-sphere blocks) is even
-  const f32x16 zero = {};
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc((void*)At, (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rw =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(Wt + (FIXED ? 32 : 0)), (short)0, 0x7fffffff, 0x00020000);
-  const int va = lane * 16, vw = h * 64;
-  auto load_a = [&](int rb, int m) {
-    if constexpr (BUF) return __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(ra, va, (2 * rb + m) * 1024, 0));
-    else return __builtin_bit_cast(bf16x8, At[(2 * rb + m) * 64 + lane]);
-  };
-  auto load_w = [&](int rb, int i) {
-    if constexpr (BUF) return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rw, vw + 16 * i, rb * 256, 0));
-    else return *reinterpret_cast<const float4*>(Wt + (FIXED ? 32 : 0) + rb * 64 + h * 16 + 4 * i);
-  };
-  auto consume = [&](const f32x16& D, int rb, int cb) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 wi = load_w(rb, i);
-      const float wv[4] = {wi.x, wi.y, wi.z, wi.w};
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        float q = D[4 * i + v];
-        if constexpr (CLAMP) q = qclamp(q, QMIN);
-        const float rho = fsqrt(q);
-        acc[cb] = fmaf(wv[v], fexp2(FIXED ? S[cb] - rho : -rho), acc[cb]);
-      }
-    }
-  };
-  bf16x8 A0 = load_a(0, 0), A1 = load_a(0, 1);
-  for (int rb = 0; rb < n32; ++rb) {
-    int z = 0;  // opaque 0: the ray-side reads stay in the loop (hoisted they hold 16 VGPRs)
-    asm volatile("" : "+s"(z));
-    const uint4* xah = xa + z;
-    const uint4* xbh = (h ? xb : xa) + z;
-    f32x16 D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A0, __builtin_bit_cast(bf16x8, xah[r]), zero, 0, 0, 0);
-    D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, __builtin_bit_cast(bf16x8, xbh[r]), D, 0, 0, 0);
-    RM_SCHED_BARRIER();
-    consume(D, rb, 0);
-    RM_SCHED_BARRIER();
-    D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A0, __builtin_bit_cast(bf16x8, xah[32 + r]), zero, 0, 0, 0);
-    D = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A1, __builtin_bit_cast(bf16x8, xbh[32 + r]), D, 0, 0, 0);
-    const int rn = min(rb + 1, n32 - 1);
-    A0 = load_a(rn, 0);
-    A1 = load_a(rn, 1);
-    RM_SCHED_BARRIER();
-    consume(D, rb, 1);
-    RM_SCHED_BARRIER();
-  }
-  // lanes < 32 end with column block 0 (rays 0-31), lanes >= 32 with block 1: ray l either way
-  const float own = swap32_sum(acc[0], acc[1]);
-  __builtin_amdgcn_wave_barrier();
-  return own;
-}
-#endif
 
 // Split march (RM_MARCH_SPLIT): the kSplitWaves waves of a block hold the same 64 rays; wave w
 // sums the row blocks [part_rb(w), part_rb(w + 1)) (even bounds: lse_mfma runs pairs) and the
@@ -1058,17 +878,13 @@ __device__ __forceinline__ float split_combine(float part, float* comb, int wave
 // A march step's soft-min D at p on the matrix cores without a shift (soft_min_march's
 // unshifted step; shared with write_origins like march_d_fixed). comb != nullptr: a split
 // block's wave, At / Wt / nrb its quarter (split_combine).
-template <bool CLAMP, bool BUF = (RM_MARCH_BUFLOAD != 0), int NCB = 4>
+template <bool CLAMP, int NCB = 4>
 __device__ __forceinline__ float march_d_none(const float p[3], float kappa, float inv_kappa,
                                               const uint4* __restrict__ At, const float* __restrict__ Wt, int nrb,
                                               uint4* xa, uint4* xb, float* xs, int lane, float* comb = nullptr,
                                               int wave = 0) {
 #pragma clang fp contract(off)
-#if RM_MFMA32
-  float s = lse_mfma32<CLAMP, false, BUF>(p, kappa * kappa, 0.0f, At, Wt, nrb, xa, xb, xs, lane);
-#else
-  float s = lse_mfma<CLAMP, false, BUF, NCB>(p, kappa * kappa, 0.0f, At, Wt, nrb, xa, xb, xs, lane);
-#endif
+  float s = lse_mfma<CLAMP, false, NCB>(p, kappa * kappa, 0.0f, At, Wt, nrb, xa, xb, xs, lane);
   if (comb != nullptr) s = split_combine(s, comb, wave, lane);
   return -flog2(fmaxf(s, 1e-30f)) * inv_kappa;
 }
@@ -1084,7 +900,7 @@ __device__ __forceinline__ float fixed_shift(const float p[3], float k2, const f
 // A march step's soft-min D at p on the matrix cores with the fixed shift sh = rho'_0 (sphere 0;
 // S00 / S10 = its records S0[0] / S1[0]) -- soft_min_march's fixed-shift step, shared with the
 // per-view origin step (write_origins) so that both give the same bits.
-template <bool CLAMP, bool BUF = (RM_MARCH_BUFLOAD != 0), int NCB = 4>
+template <bool CLAMP, int NCB = 4>
 __device__ __forceinline__ float march_d_fixed(const float p[3], float kappa, float inv_kappa, float kr_first,
                                                const float4& S00, const float4& S10, const uint4* __restrict__ At,
                                                const float* __restrict__ Wt, int nrb, uint4* xa, uint4* xb,
@@ -1092,11 +908,7 @@ __device__ __forceinline__ float march_d_fixed(const float p[3], float kappa, fl
 #pragma clang fp contract(off)
   const float k2 = kappa * kappa;
   const float sh = fixed_shift(p, k2, S00, S10);
-#if RM_MFMA32
-  float s = lse_mfma32<CLAMP, true, BUF>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane);
-#else
-  float s = lse_mfma<CLAMP, true, BUF, NCB>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane);
-#endif
+  float s = lse_mfma<CLAMP, true, NCB>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane);
   if (comb != nullptr) s = split_combine(s, comb, wave, lane);
   const float m = kr_first - sh;
   return -(flog2(fmaxf(s, 1e-30f)) + m) * inv_kappa;
@@ -1458,7 +1270,7 @@ __device__ __forceinline__ OrderSets order_sets(const KArgs& a) {
 // rays that march all their steps -- first, the cheap border tiles last, where they fill the
 // machine while the heavy blocks finish. Partials stay indexed by the logical block, so the
 // gradient sums (and every result) do not depend on the order.
-__device__ __forceinline__ long long ray_block(const KArgs& a, int* cls = nullptr) {
+__device__ __forceinline__ long long ray_block(const KArgs& a) {
   int b = blockIdx.x;
   if (a.block_order == nullptr) return b;
   // The dispatcher hands block i to XCD i % 8. With the views interleaved (b = rank * V + v),
@@ -1466,13 +1278,8 @@ __device__ __forceinline__ long long ray_block(const KArgs& a, int* cls = nullpt
   // of the scene they see): the XCDs of the dearest view finish last. Rotating the positions
   // inside every full round of 8 blocks by the round number makes each XCD cycle through all
   // views (rank order is kept up to 8 positions, so heavy tiles still start first).
-#ifndef RM_XCD_ROTATE
-#define RM_XCD_ROTATE 1
-#endif
-#if RM_XCD_ROTATE
   const int g = b >> 3;
   if ((g + 1) * 8 <= (int)gridDim.x) b = (g << 3) + (((b & 7) + g) & 7);
-#endif
   const OrderSets os = order_sets(a);
   if (os.cnt_r != nullptr) {
     // position b of the class-major concatenation of the previous launch's lists; every block
@@ -1487,10 +1294,7 @@ __device__ __forceinline__ long long ray_block(const KArgs& a, int* cls = nullpt
       }
       tot += n;
     }
-    if (tot == (int)gridDim.x && cb >= 0) {
-      if (cls != nullptr) *cls = cb;
-      return os.list_r[cb * kMaxBlocksPerLaunch + (b - base)];
-    }
+    if (tot == (int)gridDim.x && cb >= 0) return os.list_r[cb * kMaxBlocksPerLaunch + (b - base)];
   }
   const int r = b / a.order_views, v = b - r * a.order_views;
   return (long long)v * a.order_tiles + a.block_order[r];
@@ -1656,9 +1460,6 @@ __global__ __launch_bounds__(kBlock, RM_CONT_MIN_WAVES) void rm_cont_kernel(cons
 template <int MODE, bool CAM, bool SPLIT>
 __device__ __forceinline__ void ray_body(const KArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-#ifdef RM_RAY_STATS
-  __shared__ unsigned rs_w[3];  // measurement build (see the march)
-#endif
   Lds L;
   {
     const int np = a.Mpad / 2;
@@ -1680,7 +1481,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   // split wave's quarter of the row blocks, its loop bounds and fragment addresses, LDS slots --
   // stays wave-uniform for the compiler (threadIdx-derived values are otherwise vector values)
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int cls = -1;  // the block's cost class in the previous launch (cost-ordered dispatch), else -1
   long long blk;
   // ray_cont (ray mode): this block marches listed rays [32 b, 32 b + 32) of ray_list, one per lane
   // (lanes l and l + 32 the same ray); lanes past the list's end are invalid copies of its first
@@ -1694,27 +1494,15 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     listed = i < n;
     li_listed = a.ray_list[listed ? i : i0];
     blk = -1;  // no group of its own
-  } else if (SPLIT && a.cont_resume > 0) {  // continuation launch: the blocks the first launch deferred
-    // position blockIdx.x of the class-major concatenation of the class lists
-    int b = (int)blockIdx.x, c = 0;
-    for (; c < kContClasses; ++c) {
-      const int n = a.cont_count[c];
-      if (b < n) break;
-      b -= n;
-    }
-    if (c == kContClasses) return;
-    blk = a.cont_list[(long long)c * a.cont_stride + b];
+  } else if (SPLIT && a.cont_resume > 0) {  // resume launch: the groups the first launch deferred
+    if ((int)blockIdx.x >= *a.cont_count) return;
+    blk = a.cont_list[blockIdx.x];
   } else {
-    blk = ray_block(a, &cls);
+    blk = ray_block(a);
   }
   // SPLIT: lane l holds ray l mod kSplitRays of the group (kSplitRays < 64: copies, see kSplitRays)
   const long long li = li_listed >= 0 ? li_listed
                                       : (SPLIT ? blk * kSplitRays + (lane & (kSplitRays - 1)) : blk * kBlock + tid);
-#if RM_HEAVY_PRIO
-  // the dearest class's waves first at the SIMD's issue arbiter: they set the launch's critical
-  // path, the cheaper waves fill the issue slots they leave
-  if (cls >= 0 && cls < RM_HEAVY_PRIO) __builtin_amdgcn_s_setprio(2);
-#endif
   const bool valid = listed && li < a.n_rays;
   long long ri = a.ray_begin + (valid ? li : 0);  // becomes the ray's row in the [N,3] tensors
   // the wave that writes this ray's outputs; SPLIT: all four waves run the post-march forward
@@ -1740,13 +1528,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     escaped_block<MODE>(a, L, blk, ri, valid, tid, lane, wave);
     return;
   }
-#if RM_DEAD_EARLY
-  if constexpr (!SPLIT && (MODE == kBwd || MODE == kTrain)) {
-    // the hand-off's count of the waves that end early: zero before any wave can reach it
-    if (tid == 0) reinterpret_cast<int*>(L.misc)[kDeadCountSlot] = 0;
-    __syncthreads();
-  }
-#endif
 
   // Scene radius bounds from the record header: with r_min, a lower bound on the scene distance
   // proves rho_j = dist_j + r_j >= kSafeRho for every sphere, so max(q, 1e-6) cannot bind and
@@ -1889,7 +1670,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       tr_paths += 1ull << (16 * ((fixed ? 2 : 0) + (fast ? 0 : 1)));
 #endif
       float Dm;
-      constexpr bool kBuf = RM_MARCH_BUFLOAD != 0;
       const uint4* At = L.At;
       const float* Wt = L.Wt;
       int nq = nrb;
@@ -1904,11 +1684,11 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       constexpr int kNcb = SPLIT ? kSplitCB : 4;  // column blocks of this wave's rays
       if (fixed) {  // the ray's shift: rho'_0 of sphere 0 (any value near it keeps +-100 headroom)
         const float4 A = Lds::v4(L.S0[0]), B = Lds::v4(L.S1[0]);
-        Dm = fast ? march_d_fixed<false, kBuf, kNcb>(p, kappa, inv_kappa, kr_first, A, B, At, Wt, nq, xa, xb, xs, lane, comb, wave)
-                  : march_d_fixed<true, kBuf, kNcb>(p, kappa, inv_kappa, kr_first, A, B, At, Wt, nq, xa, xb, xs, lane, comb, wave);
+        Dm = fast ? march_d_fixed<false, kNcb>(p, kappa, inv_kappa, kr_first, A, B, At, Wt, nq, xa, xb, xs, lane, comb, wave)
+                  : march_d_fixed<true, kNcb>(p, kappa, inv_kappa, kr_first, A, B, At, Wt, nq, xa, xb, xs, lane, comb, wave);
       } else {
-        Dm = fast ? march_d_none<false, kBuf, kNcb>(p, kappa, inv_kappa, At, Wt, nq, xa, xb, xs, lane, comb, wave)
-                  : march_d_none<true, kBuf, kNcb>(p, kappa, inv_kappa, At, Wt, nq, xa, xb, xs, lane, comb, wave);
+        Dm = fast ? march_d_none<false, kNcb>(p, kappa, inv_kappa, At, Wt, nq, xa, xb, xs, lane, comb, wave)
+                  : march_d_none<true, kNcb>(p, kappa, inv_kappa, At, Wt, nq, xa, xb, xs, lane, comb, wave);
       }
       (void)k2;
 #ifdef RM_BLOCK_TRACE
@@ -1991,15 +1771,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   if (MODE == kBwd && a.t_in != nullptr) {
     t = a.t_in[ri];
   } else {
-#if RM_PRIO_RAMP
-    // Equalise progress of the waves sharing a SIMD: VALU issue is arbitrated by priority,
-    // then age, so without this the oldest wave races ahead and the youngest finishes last
-    // (alone, latency-bound) -- a ~14% tail when one launch fills the GPU exactly once.
-    // A wave lowers its priority as it passes checkpoints (march halves, post-march forward,
-    // backward), so laggards win the arbitration.
-    __builtin_amdgcn_s_setprio(3);
-    const int half = max(a.steps / 2, 1);
-#endif
     // Escaped rays: receding from the scene's bounding sphere (c_0, R) with every later
     // soft-min >= |p - c_0| - R - ln(M)/k >= gone_d (the distance only grows along a
     // receding ray, so t keeps increasing); the reconnected point and the mask argument
@@ -2016,10 +1787,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // rays are all gone stops (a.early_exit). The same in every mode that builds the table,
     // exit on or off, so both give the same bits.
     const float rprime = (hdr[7] + a.lse_slack + 1e-3f) * (1.0f + 1e-6f);  // R' as in write_bound
-#ifdef RM_LANE_STATS  // measurement build: lane-steps of escaped (or invalid) rays in marching waves
-    unsigned long long lane_gone_steps = 0;
-    int lanes_gone_last = 0;
-#endif
     float gone_step = 0.0f;  // dist - R' of a gone ray at the current point
     auto wave_escaped = [&](int st, const float p[3]) {
       if (!(a.gone_d > 0.0f)) return false;
@@ -2032,10 +1799,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
         steps_saved += a.steps - st;
         return true;
       }
-#ifdef RM_LANE_STATS
-      lane_gone_steps += __popcll(__ballot(gone || !valid));
-      lanes_gone_last = __popcll(__ballot(gone || !valid));
-#endif
       return false;
     };
     // A gone ray's remaining bound steps from step `from` to the end (what the march would do):
@@ -2077,32 +1840,25 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
         }
       }
     }
-    // the cycle exit's history: t one to four steps back, and the choices (3 bits per step,
+    // the cycle exit's history: t one and two steps back, and the choices (3 bits per step,
     // the latest in the low bits; 7 is no valid choice)
     float cyc_t1 = __builtin_nanf(""), cyc_t2 = __builtin_nanf("");
-#if RM_CYCLE_MAX >= 3
-    float cyc_t3 = __builtin_nanf("");
-#endif
-#if RM_CYCLE_MAX >= 4
-    float cyc_t4 = __builtin_nanf("");
-#endif
     int chist = 0xFFF;
     int rhist = 0xFFF;  // ray mode: the ray's own choice history (per lane: listed rays come from many groups)
-    static_assert(RM_CYCLE_MAX == 2 || !SPLIT, "the continuation saves two steps of history");
     if (SPLIT && a.cont_resume > 0) {  // the state the first launch saved at step cont_resume
       const float* cs = a.cont_state;
       const long long R = a.cont_rays;
-      const long long G = (SPLIT ? 8 : 7) * R;  // the per-group words after the per-ray rows
+      const long long G = 8 * R;  // the per-group words after the per-ray rows
       t = cs[li];
       lb = cs[R + li];
       Dprev = cs[2 * R + li];
       cyc_t1 = cs[3 * R + li];
       cyc_t2 = cs[4 * R + li];
-      const float gflag = cs[5 * R + li];  // ray mode: 1 gone, 2 retired; else non-zero = gone
-      gone = SPLIT ? gflag == 1.0f : gflag != 0.0f;
-      retired = SPLIT && gflag == 2.0f;
+      const float gflag = cs[5 * R + li];  // 1 gone, 2 retired
+      gone = gflag == 1.0f;
+      retired = gflag == 2.0f;
       rho_lb = cs[6 * R + li];
-      if (SPLIT) rhist = __float_as_int(cs[7 * R + li]);
+      rhist = __float_as_int(cs[7 * R + li]);
       if (!a.ray_cont) {
         chist = __float_as_int(cs[G + 2 * blk]);
         steps_saved = __float_as_int(cs[G + 2 * blk + 1]);
@@ -2110,15 +1866,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       st0 = a.cont_resume;
     }
     const unsigned long long below = (1ull << lane) - 1ull;
-#ifdef RM_RAY_STATS  // measurement build: the march steps each ray needs (until gone or period 2)
-    int ray_need = st0;
-    // and what packing a block's rays still marching at step RM_RAY_STATS_CAP into the fewest
-    // waves would leave of its waves' steps after it (unsplit): live rays, summed steps, max steps
-    if (tid < 3) rs_w[tid] = 0u;
-    __syncthreads();
-    bool rs_at = false;
-    int rs_last = st0 - 1;
-#endif
     for (int st = st0; !dead && st < a.steps; ++st) {
       if (SPLIT && a.cont_cap > 0 && st == a.cont_cap) {
         // ray mode, defer at the top of this step: every ray's state, the marching rays to the
@@ -2157,29 +1904,15 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
         }
         return;
       }
-#if RM_PRIO_RAMP
-      if (st == half) __builtin_amdgcn_s_setprio(2);
-#endif
       const float p[3] = {fmaf(d[0], t, o[0]), fmaf(d[1], t, o[1]), fmaf(d[2], t, o[2])};
       if (wave_escaped(st, p)) {
         dead = true;
         st_stop = st;
         break;
       }
-#ifdef RM_RAY_STATS
-      if (!SPLIT && st == RM_RAY_STATS_CAP) {
-        const int lv = __popcll(__ballot(valid && !gone && ray_need >= st));
-        if (lane == 0) atomicAdd(&rs_w[0], (unsigned)lv);
-        rs_at = true;
-      }
-      rs_last = st;
-#endif
       int choice;
       const float D = soft_min_march(p, all_safe(lb, rho_lb), Dprev, choice);
       const float t_step = t;  // this step's state: (t_step, choice)
-#ifdef RM_RAY_STATS
-      if (valid && !gone && !(t_step == cyc_t2 && choice == ((chist >> 3) & 7))) ray_need = st + 1;
-#endif
       if constexpr (SPLIT) {
         // Ray mode: a ray's step is a function of its own t (the shift is scene-uniform; the clamp
         // choice changes no bit), so a ray whose t repeats with period 2 (t_step == t two steps
@@ -2227,22 +1960,15 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       Dprev = D;
       // Cycle exit (exact). A march step is a deterministic function of the wave's state: the t
       // of every ray that is not gone and the step's wave-uniform choice (which carries all the
-      // previous step's D decides). When this step's state equals the state P steps back (P = 2,
-      // or up to RM_CYCLE_MAX) the march repeats with period P from there, so the state after
-      // the last step is the one (steps left) mod P steps after that earlier state. A ray cycling
+      // previous step's D decides). When this step's state equals the state P = 2 steps back
+      // the march repeats with period P from there, so the state after the last step is the
+      // one (steps left) mod P steps after that earlier state. A ray cycling
       // between fixed points cannot become gone later (its thresholds only grow); gone rays take
       // their remaining bound steps here, as the march would. Of the last step's D the post-march
       // needs only the clamp-free choice of the reconnect: the final state's choice bit 2.
       if (a.early_exit && MODE != kRender) {
-        int P = 0;
-        if (choice == ((chist >> 3) & 7) && __all(gone || t_step == cyc_t2)) P = 2;
-#if RM_CYCLE_MAX >= 3
-        else if (choice == ((chist >> 6) & 7) && __all(gone || t_step == cyc_t3)) P = 3;
-#endif
-#if RM_CYCLE_MAX >= 4
-        else if (choice == ((chist >> 9) & 7) && __all(gone || t_step == cyc_t4)) P = 4;
-#endif
-        if (P != 0) {
+        if (choice == ((chist >> 3) & 7) && __all(gone || t_step == cyc_t2)) {
+          constexpr int P = 2;
           // the state after the last step (step a.steps) is this step's state or the one `back`
           // steps before it; `left` steps remain after this one
           const int left = a.steps - 1 - st, m = a.steps - st, back = (P - m % P) % P;
@@ -2250,12 +1976,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
           if (!gone) {
             if (back == 0) t = t_step;
             else if (back == 1) t = cyc_t1;
-#if RM_CYCLE_MAX >= 3
-            else if (back == 2) t = cyc_t2;
-#endif
-#if RM_CYCLE_MAX >= 4
-            else if (back == 3) t = cyc_t3;
-#endif
             lb = (cf & 4) ? INFINITY : -INFINITY;  // all_safe(lb, rho_lb) of the final state = its bit 2
             rho_lb = -INFINITY;
           } else {
@@ -2270,29 +1990,11 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
 #endif
           break;
         }
-#if RM_CYCLE_MAX >= 4
-        cyc_t4 = cyc_t3;
-#endif
-#if RM_CYCLE_MAX >= 3
-        cyc_t3 = cyc_t2;
-#endif
         cyc_t2 = cyc_t1;
         cyc_t1 = t_step;
         chist = ((chist << 3) | choice) & 0xFFF;
       }
     }
-#ifdef RM_RAY_STATS
-    if (!SPLIT && a.stats != nullptr) {  // stats[3]: the needed lane-steps, summed
-      unsigned long long v = valid ? (unsigned long long)ray_need : 0ull;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-      if (lane == 0) atomicAdd(a.stats + 3, v);
-      if (rs_at && lane == 0) {
-        atomicAdd(&rs_w[1], (unsigned)(rs_last + 1 - RM_RAY_STATS_CAP));
-        atomicMax(&rs_w[2], (unsigned)(rs_last + 1 - RM_RAY_STATS_CAP));
-      }
-    }
-#endif
     if (SPLIT && a.ray_cont) {
       // ray mode: the listed rays' final states back into their groups' rows (the resume launch
       // runs the groups' post-march forward and backward); the steps this block ran uncounted
@@ -2319,14 +2021,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   RM_TRACE(10, __builtin_readcyclecounter() - tr_c_begin);
   RM_TRACE(11, tr_cyc);
 #endif
-#ifdef RM_LANE_STATS  // stats[3] += escaped lane-steps of the march + 5 sweeps per escaped lane of a live wave
-    if (a.stats != nullptr && lane == 0)
-      atomicAdd(a.stats + 3, lane_gone_steps + (dead ? 0ull : 5ull * (unsigned long long)lanes_gone_last));
-#endif
   }
-#if RM_PRIO_RAMP
-  __builtin_amdgcn_s_setprio(1);
-#endif
   if ((MODE == kFwd || MODE == kRender) && a.t_out != nullptr && valid && own_rays) a.t_out[ri] = t;
   // work statistics: per wave here in the forward modes; per block at the hand-off barrier in the
   // backward modes (one pair of atomics per block, not per wave)
@@ -2473,9 +2168,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   }
   RM_TRACE(5, __builtin_amdgcn_s_memrealtime());
   if constexpr (MODE == kFwd || MODE == kRender) return;
-#if RM_PRIO_RAMP
-  __builtin_amdgcn_s_setprio(0);
-#endif
 
   // ---- seed g = dL/dout
   float g[3] = {0.0f, 0.0f, 0.0f};
@@ -2511,8 +2203,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   const float b_scale = cmu * frcp(Zb);
 
   float* rec = a.partials + blk * a.rec;
-  float* slots = L.slots;
-  int chunk_ctr = 0;
 
   // ---- per-ray scalars (light before the projection, ambient, loss) and the early-exit
   // hand-off: every wave publishes its scalar sums and whether it left the march early; after
@@ -2562,32 +2252,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       rec[(long long)a.Mpad * 8 + lane] = acc;
     }
   };
-#if RM_DEAD_EARLY
-  if constexpr (!SPLIT) {
-    if (dead) {
-      // This wave's rays all escaped and its sums are published: it ends here rather than at the
-      // barrier below (an ended wave no longer counts in s_barrier), so its slot is free while the
-      // block's other waves march on. The count of such waves says which one was last; when every
-      // wave of the block left early, that one does the block's hand-off work (the others'
-      // publications precede their adds to the count: LDS operations of a wave run in order).
-      int* dcnt = reinterpret_cast<int*>(L.misc) + kDeadCountSlot;
-      int prev = 0;
-      if (lane == 0) prev = __hip_atomic_fetch_add(dcnt, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
-      prev = __shfl(prev, 0);
-      if (prev != kWaves - 1) return;
-      if (lane == 0) handoff_work();
-      escaped_record();
-      return;
-    }
-  }
-#endif
   __syncthreads();
-#ifdef RM_RAY_STATS
-  if (!SPLIT && tid == 0 && a.stats != nullptr && rs_w[1] != 0u) {
-    atomicAdd(a.stats + 6, 64ull * rs_w[1]);
-    atomicAdd(a.stats + 7, 64ull * ((rs_w[0] + 63u) / 64u) * rs_w[2]);
-  }
-#endif
   int alive = 0;
 #pragma unroll
   for (int w = 0; w < (SPLIT ? kSplitWaves : kWaves); ++w) alive |= wflag[w] ? 0 : (1 << w);
@@ -2599,21 +2264,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     return;
   }
   const int arank = __popc(alive & ((1 << wave) - 1));
-  const int atid = arank * 64 + lane, astride = __popc(alive) * 64;
-  // sum of the live waves' slots, in wave order (the order the all-alive case uses)
-  auto live_sum = [&](const float* s0, int stride) {
-    float acc = 0.0f;
-    bool first = true;
-#pragma unroll
-    for (int w = 0; w < (SPLIT ? kSplitWaves : kWaves); ++w)
-      if (alive & (1 << w)) {
-        acc = first ? s0[w * stride] : acc + s0[w * stride];
-        first = false;
-      }
-    return acc;
-  };
 
-#if RM_BWD_TRANSPOSED
   // ---- backward sweeps with one sphere per lane (transposed), the work shared out over the
   // block's live waves. Each live wave publishes its rays with non-zero seeds (a source) as a
   // compacted field-major LDS image. The work units are (64-sphere group, source wave) pairs in
@@ -2636,11 +2287,6 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   // (qpair, delta_pair_rsq), so dd = dmin - delta <= 0 and v - mA <= 0 hold exactly.
   bool any_seed = true;  // block-uniform: some ray of the block has a non-zero seed
   {
-    (void)slots;
-    (void)live_sum;
-    (void)chunk_ctr;
-    (void)atid;
-    (void)astride;
     constexpr int kFields = kBwdFields;  // sweep 1: px py pz |p|^2 dmin 1/Zw b_scale mg gm.xyz d.xyz (14); sweep 2: 6
     constexpr int kWv = SPLIT ? kSplitWaves : kWaves;
     float* rayf_all = L.slots;                     // [wave][field][64 ray slots]; after a sweep: partials
@@ -2814,11 +2460,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
                 }
                 const int s0 = 2 * (b + uu);
                 const f2 PX = pair(sw, 0, s0), PY = pair(sw, 1, s0), PZ = pair(sw, 2, s0);
-#if RM_BWD_PSQ_REG
-                const f2 PP = fma2(PZ, PZ, fma2(PY, PY, PX * PX));  // == psq(p), lane by lane
-#else
                 const f2 PP = pair(sw, 3, s0);
-#endif
                 const f2 DM = pair(sw, 4, s0), IZ = pair(sw, 5, s0), BS = pair(sw, 6, s0), MG = pair(sw, 7, s0);
                 const f2 G0 = pair(sw, 8, s0), G1 = pair(sw, 9, s0), G2 = pair(sw, 10, s0);
                 const f2 DX = pair(sw, 11, s0), DY = pair(sw, 12, s0), DZ = pair(sw, 13, s0);
@@ -2947,11 +2589,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
             for (int i2 = 0; i2 < nps; ++i2) {
               const int s0 = 2 * i2;
               const f2 PX = pair(sw, 0, s0), PY = pair(sw, 1, s0), PZ = pair(sw, 2, s0);
-#if RM_BWD_PSQ_REG
-              const f2 PP = fma2(PZ, PZ, fma2(PY, PY, PX * PX));  // == psq(pa), lane by lane
-#else
               const f2 PP = pair(sw, 3, s0);
-#endif
               const f2 MA = pair(sw, 4, s0), HS = pair(sw, 5, s0);
               f2 q = fma2(PZ, GZ, fma2(PY, GY, fma2(PX, GX, PP + CC)));  // == qpair: the reconnect sweep's q
               const f2 qraw = q;
@@ -2996,803 +2634,18 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     }
   }
   __syncthreads();
-#else
-  // ---- backward sweep 1 at p_final: colour softmax + mask soft-min + p_final(t_final)
-  f2 GP[3] = {sp(0.0f), sp(0.0f), sp(0.0f)};
-  {
-    const f2 PX = sp(p[0]), PY = sp(p[1]), PZ = sp(p[2]), PP = sp(psq(p)), CL = sp(c10l), KA = sp(kappa),
-             DM = sp(dmin), IZ = sp(invZw), BS = sp(b_scale), G0 = sp(gm[0]), G1 = sp(gm[1]), G2 = sp(gm[2]),
-             MG = sp(mg), NCS = sp(-a.csharp), HALF = sp(0.5f);
-    auto sweep1 = [&](auto clamp_tag, int t0, int tn) {
-      constexpr bool CLAMP = decltype(clamp_tag)::value;
-      for (int jc = 0; jc < tn; jc += kChunkBwd, ++chunk_ctr) {
-        float* sb = slots + (chunk_ctr & 1) * (kWaves * kChunkBwd * 8);
-        for (int jj = 0; jj < kChunkBwd; jj += 4) {  // 4 spheres (2 pairs) per masked LDS write
-          float red[4];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int i = (jc + jj) / 2 + u;
-            const float4 A = L.p0(i), B = L.p1(i), R = L.p2(i), C3 = L.p3(i);
-            const float2 C4 = L.p4(i);
-            f2 q, ir;
-            const f2 dl = delta_pair_rsq<CLAMP>(PX, PY, PZ, PP, A, B, R, q, ir);  // bitwise the shade sweep's
-            const f2 dd = DM - dl;  // <= 0 exactly
-            const f2 w = exp2v(dd * CL) * IZ;
-            const f2 bt = exp2v(dd * KA) * BS;
-            const f2 cg = fma2(f2{C4.x, C4.y}, G2, fma2(hi(C3), G1, lo(C3) * G0));
-            const f2 gd = fma2(w * NCS, cg - MG, bt);
-            f2 gu = gd * ir;
-            if constexpr (CLAMP) {  // clamp_min(1e-6) gate
-              gu.x = q.x >= 1e-6f ? gu.x : 0.0f;
-              gu.y = q.y >= 1e-6f ? gu.y : 0.0f;
-            }
-            const f2 ex = fma2(HALF, lo(A), PX), ey = fma2(HALF, hi(A), PY), ez = fma2(HALF, lo(B), PZ);
-            GP[0] = fma2(gu, ex, GP[0]);
-            GP[1] = fma2(gu, ey, GP[1]);
-            GP[2] = fma2(gu, ez, GP[2]);
-            const f2 ngu = -gu;
-            const f2 v0 = ngu * ex, v1 = ngu * ey, v2 = ngu * ez, v4 = w * G0, v5 = w * G1, v6 = w * G2;
-            const float va[8] = {v0.x, v1.x, v2.x, -gd.x, v4.x, v5.x, v6.x, 0.0f};
-            const float vb[8] = {v0.y, v1.y, v2.y, -gd.y, v4.y, v5.y, v6.y, 0.0f};
-            red[2 * u] = wave_reduce8(va, lane);
-            red[2 * u + 1] = wave_reduce8(vb, lane);
-          }
-          if ((lane & 7) == 7) {
-            float* dst = sb + (wave * kChunkBwd + jj) * 8 + (lane >> 3);
-#pragma unroll
-            for (int k2 = 0; k2 < 4; ++k2) dst[8 * k2] = red[k2];
-          }
-        }
-        __syncthreads();
-        for (int e = atid; e < kChunkBwd * 8; e += astride) rec[(long long)(t0 + jc) * 8 + e] = live_sum(sb + e, kChunkBwd * 8);
-      }
-    };
-    if (fast_f)
-      for_tiles([&](int t0, int tn) { sweep1(std::false_type{}, t0, tn); });
-    else
-      for_tiles([&](int t0, int tn) { sweep1(std::true_type{}, t0, tn); });
-  }
-  __syncthreads();
-
-  // ---- backward sweep 2 at p_approx: t_final = t + D(p_approx) -> g_t * softmax(-k dist_a)
-  const float gp[3] = {GP[0].x + GP[0].y, GP[1].x + GP[1].y, GP[2].x + GP[2].y};
-  const float gt = fmaf(gp[2], d[2], fmaf(gp[1], d[1], gp[0] * d[0]));
-  {
-    const f2 PX = sp(pa[0]), PY = sp(pa[1]), PZ = sp(pa[2]), PP = sp(psq(pa)), NK = sp(nkappa), MA = sp(mA),
-             HS = sp(gt * frcp(sA)), HALF = sp(0.5f);
-    auto sweep2 = [&](auto clamp_tag, int t0, int tn) {
-      constexpr bool CLAMP = decltype(clamp_tag)::value;
-      for (int jc = 0; jc < tn; jc += kChunkBwd, ++chunk_ctr) {
-        float* sb = slots + (chunk_ctr & 1) * (kWaves * kChunkBwd * 8);
-        for (int jj = 0; jj < kChunkBwd; jj += 4) {  // 2 pairs per masked LDS write
-          float red[2];
-#pragma unroll
-          for (int u = 0; u < 2; ++u) {
-            const int i = (jc + jj) / 2 + u;
-            const float4 A = L.p0(i), B = L.p1(i);
-            const float2 K = L.kr(i);
-            f2 q = qpair(PX, PY, PZ, PP, A, B);  // bitwise the reconnect sweep's q
-            const f2 qraw = q;
-            if constexpr (CLAMP) q = clamp_q(q);
-            const f2 r = rsq2(q);  // rho = q rsq(q) as in lse_point, 1/rho = rsq(q)
-            const f2 h = exp2v(fma2(q * r, NK, f2{K.x, K.y}) - MA) * HS;  // v - mA <= 0 exactly
-            f2 hu = h * r;
-            if constexpr (CLAMP) {
-              hu.x = qraw.x >= 1e-6f ? hu.x : 0.0f;
-              hu.y = qraw.y >= 1e-6f ? hu.y : 0.0f;
-            }
-            const f2 nhu = -hu;
-            const f2 v0 = nhu * fma2(HALF, lo(A), PX), v1 = nhu * fma2(HALF, hi(A), PY),
-                     v2 = nhu * fma2(HALF, lo(B), PZ);
-            const float vals[8] = {v0.x, v1.x, v2.x, -h.x, v0.y, v1.y, v2.y, -h.y};
-            red[u] = wave_reduce8(vals, lane);
-          }
-          if ((lane & 7) == 7) {
-            float* dst = sb + (wave * kChunkBwd + jj) * 4 + (lane >> 3);
-            dst[0] = red[0];
-            dst[8] = red[1];
-          }
-        }
-        __syncthreads();
-        for (int e = atid; e < kChunkBwd * 4; e += astride) {  // added to sweep 1's columns 0-3
-          float* dst = rec + (long long)(t0 + jc + (e >> 2)) * 8 + (e & 3);
-          *dst += live_sum(sb + e, kChunkBwd * 4);
-        }
-      }
-    };
-    if (fast_a)
-      for_tiles([&](int t0, int tn) { sweep2(std::false_type{}, t0, tn); });
-    else
-      for_tiles([&](int t0, int tn) { sweep2(std::true_type{}, t0, tn); });
-  }
-  __syncthreads();
-
-#endif  // RM_BWD_TRANSPOSED
 
   // ---- per-ray scalar totals of the block (published before the sweeps)
   if (arank == 0 && lane < 8) {
     float acc = wscal[lane];
 #pragma unroll
     for (int w = 1; w < (SPLIT ? kSplitWaves : kWaves); ++w) acc += wscal[w * 8 + lane];
-#if RM_BWD_TRANSPOSED
     const float live = any_seed ? 1.0f : 0.0f;
-#else
-    const float live = 1.0f;
-#endif
     rec[(long long)a.Mpad * 8 + lane] = lane == 7 ? live : acc;  // scalar 7: live flag
   }
 }
 
-// ---- cross-block reduction (fixed order => deterministic) --------------------------------
-// Partial record of one ray block (rec = Mpad*8 + 8 floats):
-//   [Mpad][8] (gc.xyz, gr, gcol.rgb, 0) -- backward sweep 1's terms, sweep 2's (gc, gr) terms added
-//   by the block itself -- | 8 scalars
-// Scalar 7 is the block's live flag: 0 when every wave of the block left the march early or no ray
-// of it has a non-zero backward seed (its per-sphere columns are all zero and were not written),
-// 1 otherwise.
-// Output columns (ncols = Mpad*8 + 8): [Mpad][8] combined per-sphere grads | 8 scalars.
-//
-// Pass 1, grid (column blocks x segments of ray blocks): each block sums its segment for its 256
-// columns into S[seg][col] -- one addition chain per column in ray-block order, loads batched
-// eight rows at a time. Rows of dead
-// blocks are skipped: they only hold zeros, and adding +0 leaves a chain unchanged, so the sums
-// are those of the full chain.
-struct FinalArgs {
-  const float* light_dir;
-  float *gc, *gcol, *gr, *gld, *gamb, *loss_sum;
-  int accumulate;
-  int* oturn;  // nullable: the cost-order turn word the reduction advances (KArgs::oturn)
-  // rm_train_step_camera_adam on a model of M <= kOptSmallMaxM spheres: the optimizer step on the
-  // packed gradient (grad = gc: the packed layout) runs in the reduction's last block
-  // (fused_optimizer); raw == nullptr otherwise
-  float *raw, *m1, *m2, *act_out, *loss_penalty;
-  _Float16* col_h;
-  rm_step_scalars* sdev;
-  unsigned* opt_arrival;  // the column blocks' arrival counter (zero between launches)
-  int step, with_pen;
-  float lr, wd;
-};
-__device__ void fused_optimizer(const FinalArgs& f, int M);
-
-#ifndef RM_REDUCE_BATCH
-#define RM_REDUCE_BATCH 8
-#endif
-constexpr int kReduceBatch = RM_REDUCE_BATCH;  // partial rows in flight per thread
-#ifndef RM_FIN_U
-#define RM_FIN_U 16  // finalize_block: 4 * RM_FIN_U loads in flight (32 with batch 16: no gain at C2)
-#endif
-static_assert((kReduceSegs / 4) % RM_FIN_U == 0, "finalize_block rounds");
-
-__device__ void finalize_block(const float* S, int nseg, int M, int Mpad, const FinalArgs& f, float* tot);
-
-// Segments of the reduction of nblocks ray blocks: kReduceSegs, or as many multiples of 64 as a
-// launch of more than kReduceSegs * 256 blocks needs (a segment's rows fit pass 1's 256-entry list)
-__host__ __device__ inline int reduce_segs(long long nblocks) {
-  const long long need = (nblocks + 255) / 256;
-  return need <= kReduceSegs ? kReduceSegs : (int)((need + 63) / 64 * 64);
-}
-
-__global__ __launch_bounds__(256) void rm_reduce_partials(const float* __restrict__ P, long long rec, int M, int Mpad,
-                                                          int nblocks, int seg_len, float* __restrict__ S,
-                                                          const FinalArgs f, unsigned* __restrict__ arrivals) {
-  __shared__ int rows[256];
-  __shared__ int wcount[4];
-  __shared__ float tot[256];
-  __shared__ int last;
-  const int ncols = Mpad * 8 + 8;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // the launch whose partials these are has finished: the cost-ordered dispatch turns one set on
-  if (f.oturn != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) *f.oturn = (*f.oturn + 1) % 3;
-  const int col = blockIdx.x * 256 + tid;
-  const bool scalars = (int)blockIdx.x * 256 >= Mpad * 8;  // the column block of the 8 scalars
-  const int b0 = blockIdx.y * seg_len;
-  const int b1 = min(b0 + seg_len, nblocks);
-  // rows of this segment to visit, in order: every row for the scalars, live rows otherwise
-  {
-    const int b = b0 + tid;
-    const bool take = b < b1 && (scalars || P[(long long)b * rec + (long long)Mpad * 8 + 7] != 0.0f);
-    const unsigned long long m = __ballot(take);
-    if (lane == 0) wcount[wave] = __popcll(m);
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wcount[w];
-    if (take) rows[base + __popcll(m & ((1ull << lane) - 1))] = b;
-    __syncthreads();
-  }
-  const int nrows = wcount[0] + wcount[1] + wcount[2] + wcount[3];
-  if (col < ncols) {
-    float acc = 0.0f;  // columns map 1:1 onto the record (per-sphere block, then the scalars)
-    for (int i0 = 0; i0 < nrows; i0 += kReduceBatch) {
-      float v1[kReduceBatch];
-#pragma unroll
-      for (int u = 0; u < kReduceBatch; ++u) v1[u] = P[(long long)rows[min(i0 + u, nrows - 1)] * rec + col];
-#pragma unroll
-      for (int u = 0; u < kReduceBatch; ++u)
-        if (i0 + u < nrows) acc += v1[u];
-    }
-    if (arrivals == nullptr) S[(long long)blockIdx.y * ncols + col] = acc;
-    else __hip_atomic_store(S + (long long)blockIdx.y * ncols + col, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (arrivals == nullptr) return;
-  // Pass 2 in the same launch: the segment block that arrives last for this column block sums
-  // the segments and scatters them (finalize_block, the bits of rm_finalize_grads). Hand-off
-  // (MI355X_MICROARCH.md, inter-workgroup visibility): write-through segment stores drained by
-  // every wave before the block barrier, one lane's agent-scope arrival, an agent-scope acquire
-  // and write-through-cache loads in the last block -- the guide's write-through variant of the
-  // counter hand-off, which needs no release fence (cdna_hip_programming.md §5 split-K item 2);
-  // stressed under uneven load against the two-launch reduction in tests/test_gpu_fusion.py.
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(arrivals + blockIdx.x * RM_RED_ARR_STRIDE, 1u, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-    last = prev == gridDim.y - 1 ? 1 : 0;
-  }
-  __syncthreads();
-  if (!last) return;
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
-  finalize_block(S, (int)gridDim.y, M, Mpad, f, tot);
-  if (tid == 0) __hip_atomic_store(arrivals + blockIdx.x * RM_RED_ARR_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (f.raw == nullptr) return;
-  // the optimizer step on the whole gradient, by the column block that finishes last: the same
-  // write-through hand-off one level up (finalize_block stored its gradient elements write-through)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(f.opt_arrival, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = prev == gridDim.x - 1 ? 1 : 0;
-  }
-  __syncthreads();
-  if (!last) return;
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
-  fused_optimizer(f, M);
-  if (tid == 0) __hip_atomic_store(f.opt_arrival, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Pass 2 for the 256 columns of pass-1 column block blockIdx.x, by the block of that column block
-// that arrived last: thread t sums column t's kReduceSegs segments in the four chains s mod 4 of
-// rm_finalize_grads, combined (a0 + a1) + (a2 + a3) -- the same bits -- then the scatter.
-// The light-direction gradient: light_grad (contraction off), the same function in both pass-2
-// forms (finalize_block, rm_finalize_grads) and in the small kernel's final block.
-
-// a gradient element of the final scatter: write-through when the fused optimizer reads it
-__device__ __forceinline__ void put_grad(const FinalArgs& f, float* dst, float v) {
-  const float x = f.accumulate ? *dst + v : v;
-  if (f.raw != nullptr) __hip_atomic_store(dst, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *dst = x;
-}
-__device__ void finalize_block(const float* S, int nseg, int M, int Mpad, const FinalArgs& f, float* tot) {
-  const int ncols = Mpad * 8 + 8;
-  const int tid = threadIdx.x;
-  const int col = blockIdx.x * 256 + tid;
-  const int c = min(col, ncols - 1);
-  // kU * 4 loads in flight per thread (the last block runs alone: registers are free)
-  constexpr int kU = RM_FIN_U;
-  float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  for (int u0 = 0; u0 < nseg / 4; u0 += kU) {
-    float v[kU][4];
-#pragma unroll
-    for (int u = 0; u < kU; ++u)
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        v[u][k] = __hip_atomic_load(S + (long long)(4 * (u0 + u) + k) * ncols + c, __ATOMIC_RELAXED,
-                                    __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int u = 0; u < kU; ++u)
-#pragma unroll
-      for (int k = 0; k < 4; ++k) a[k] += v[u][k];
-  }
-  tot[tid] = (a[0] + a[1]) + (a[2] + a[3]);
-  __syncthreads();
-  if (col >= ncols) return;
-  if (col < Mpad * 8) {
-    const int j = col >> 3, comp = col & 7;
-    if (j >= M || comp == 7) return;
-    const float v = tot[tid];
-    float* dst = comp < 3 ? (f.gc ? f.gc + 3 * j + comp : nullptr)
-                          : (comp == 3 ? (f.gr ? f.gr + j : nullptr) : (f.gcol ? f.gcol + 3 * j + (comp - 4) : nullptr));
-    if (dst) put_grad(f, dst, v);
-    return;
-  }
-  const int sc = col - Mpad * 8;  // the scalars open their column block (Mpad * 8 % 256 == 0)
-  if (sc == 0 && f.gld) {
-    const float r[3] = {tot[tid], tot[tid + 1], tot[tid + 2]};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) put_grad(f, f.gld + k, light_grad(r, f.light_dir, k));
-  } else if (sc == 3 && f.gamb) {
-    put_grad(f, f.gamb, tot[tid]);
-  } else if (sc == 4 && f.loss_sum) {
-    f.loss_sum[0] = f.accumulate ? f.loss_sum[0] + tot[tid] : tot[tid];
-  }
-}
-
-// Pass 2 as its own launch (RM_REDUCE_FUSED=0): sum the segments in order and scatter into the
-// caller's gradient layout.
-// gld = (g_ell - ldn (ldn . g_ell)) / |ld| applies the Jacobian of ld / |ld| (renderer_diff.rs:49-50).
-__global__ __launch_bounds__(256) void rm_finalize_grads(const float* __restrict__ S, int nseg, int M, int Mpad,
-                                                         FinalArgs f) {
-  // 64 columns per block, four threads per column: thread (chain k, column) sums the segments
-  // s = k mod 4 in order -- the four chains of one thread's former loop (a[s & 3] += v[s]) --
-  // and the chains are combined as before, (a0 + a1) + (a2 + a3): the same bits, the loads
-  // spread over four times as many CUs
-  __shared__ float part[4][64];
-  const int ncols = Mpad * 8 + 8;
-  const int cl = threadIdx.x & 63, chain = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + cl;
-  static_assert(kReduceSegs % 64 == 0, "four chains of 16-load rounds");
-  {
-    // nseg (reduce_segs: a multiple of 64) segments, chain `chain` sums s = chain mod 4 in order,
-    // kReduceSegs / 4 loads in flight
-    constexpr int kC = kReduceSegs / 4;
-    const int c = min(col, ncols - 1);
-    float acc = 0.0f;
-    for (int u0 = 0; u0 < nseg / 4; u0 += kC) {
-      float v[kC];
-#pragma unroll
-      for (int u = 0; u < kC; ++u) v[u] = u0 + u < nseg / 4 ? S[(long long)(4 * (u0 + u) + chain) * ncols + c] : 0.0f;
-#pragma unroll
-      for (int u = 0; u < kC; ++u)
-        if (u0 + u < nseg / 4) acc += v[u];
-    }
-    part[chain][cl] = acc;
-  }
-  __syncthreads();
-  if (chain != 0 || col >= ncols) return;
-  auto seg_sum = [&](int l) { return (part[0][l] + part[1][l]) + (part[2][l] + part[3][l]); };
-  if (col < Mpad * 8) {
-    const int j = col >> 3, comp = col & 7;
-    if (j >= M || comp == 7) return;
-    const float v = seg_sum(cl);
-    float* dst = comp < 3 ? (f.gc ? f.gc + 3 * j + comp : nullptr)
-                          : (comp == 3 ? (f.gr ? f.gr + j : nullptr) : (f.gcol ? f.gcol + 3 * j + (comp - 4) : nullptr));
-    if (dst) *dst = f.accumulate ? *dst + v : v;
-    return;
-  }
-  const int sc = col - Mpad * 8;  // Mpad * 8 is a multiple of 64: the scalars open their block
-  if (sc == 0 && f.gld) {
-    const float r[3] = {seg_sum(cl), seg_sum(cl + 1), seg_sum(cl + 2)};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float gv = light_grad(r, f.light_dir, c);
-      f.gld[c] = f.accumulate ? f.gld[c] + gv : gv;
-    }
-  } else if (sc == 3 && f.gamb) {
-    const float v = seg_sum(cl);
-    f.gamb[0] = f.accumulate ? f.gamb[0] + v : v;
-  } else if (sc == 4 && f.loss_sum) {
-    const float v = seg_sum(cl);
-    f.loss_sum[0] = f.accumulate ? f.loss_sum[0] + v : v;
-  }
-}
-
-// ---- model helpers (scene.rs:41-45, training.rs:38-82, Burn Adam) -------------------------
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-// burn::tensor::activation::softplus(x, 1) = log(1 + exp(x))
-__device__ __forceinline__ float softplusf_(float x) { return logf(1.0f + expf(x)); }
-
-// scene.rs:41-45 on packed element i (layout [centers 3M | colors 3M | radius M | light 3 | ambient 1]).
-__device__ __forceinline__ float activate_elem(float x, int i, int M) {
-#pragma clang fp contract(off)
-  if (i < 3 * M) return x;                           // centers
-  if (i < 6 * M) return sigmoidf_(x);                // colors = sigmoid(raw)        scene.rs:41
-  if (i < 7 * M) return softplusf_(x) + 0.01f;       // radius = softplus(raw)+0.01  scene.rs:43
-  if (i < 7 * M + 3) return x;                       // light_dir raw                scene.rs:44
-  return sigmoidf_(x);                               // ambient = sigmoid(raw)       scene.rs:45
-}
-
-// dataset.rs:75-79: rows idx[i] of the ray / target arrays -> the batch (3 floats per row per
-// array). An index outside [0, num_src) yields a zero row rather than an out-of-bounds read.
-__global__ __launch_bounds__(256) void rm_gather_kernel(const float* __restrict__ org, const float* __restrict__ dir,
-                                                        const float* __restrict__ tgt, long long num_src,
-                                                        const int32_t* __restrict__ idx, long long n,
-                                                        float* __restrict__ oo, float* __restrict__ od,
-                                                        float* __restrict__ ot) {
-  const long long e = (long long)blockIdx.x * 256 + threadIdx.x;  // one float of the [n,3] batch
-  if (e >= 3 * n) return;
-  const long long i = e / 3;
-  const int c = (int)(e - 3 * i);
-  const long long j = idx[i];
-  const bool ok = j >= 0 && j < num_src;
-  const long long s = 3 * j + c;
-  if (oo) oo[e] = ok ? org[s] : 0.0f;
-  if (od) od[e] = ok ? dir[s] : 0.0f;
-  if (ot) ot[e] = ok ? tgt[s] : 0.0f;
-}
-
-// SceneDataset::sample_batch on the device (dataset.rs:47-82): batch row i draws its pixel from
-// a counter-based generator -- splitmix64 over key + (i + 1) * golden, the key mixing (seed,
-// stream, counter) -- so a draw depends only on its position, not on the launch geometry: rows
-// i < n_uniform take a pixel uniformly from [0, num_src), the rest a foreground pixel uniformly
-// from fg[0, num_fg) (the index is the high 64 bits of r * n: bias n / 2^64). Then the row's
-// ray origin, direction and target are gathered (dataset.rs:75-79). One thread per row.
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long z) {
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__global__ __launch_bounds__(256) void rm_sample_kernel(const float* __restrict__ org, const float* __restrict__ dir,
-                                                        const float* __restrict__ tgt, long long num_src,
-                                                        const int32_t* __restrict__ fg, long long num_fg,
-                                                        long long n_uniform, long long n, unsigned long long key,
-                                                        float* __restrict__ oo, float* __restrict__ od,
-                                                        float* __restrict__ ot, int32_t* __restrict__ idx_out) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const unsigned long long r = splitmix64(key + (unsigned long long)(i + 1) * 0x9E3779B97F4A7C15ull);
-  long long j;
-  if (i < n_uniform) j = (long long)__umul64hi(r, (unsigned long long)num_src);
-  else j = fg[__umul64hi(r, (unsigned long long)num_fg)];
-  if (idx_out) idx_out[i] = (int32_t)j;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if (oo) oo[3 * i + c] = org[3 * j + c];
-    if (od) od[3 * i + c] = dir[3 * j + c];
-    if (ot) ot[3 * i + c] = tgt[3 * j + c];
-  }
-}
-
-__global__ __launch_bounds__(256) void rm_activate_kernel(const float* __restrict__ raw, int M,
-                                                          float* __restrict__ act) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 7 * M + 4) return;
-  act[i] = activate_elem(raw[i], i, M);
-}
-
-// Block reduction of 4 floats over 256 threads in fixed tree order (deterministic).
-__device__ __forceinline__ void block_sum4(float (&v)[4], float* red) {
-#pragma unroll
-  for (int c = 0; c < 4; ++c) red[c * 256 + threadIdx.x] = v[c];
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) red[c * 256 + threadIdx.x] += red[c * 256 + threadIdx.x + w];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int c = 0; c < 4; ++c) v[c] = red[c * 256];
-}
-
-// Repulsion row of sphere s (training.rs:73-82) over j = j0, j0 + stride, ... < M, added to v:
-// dist_sj = sqrt(max(|c_s|^2 + |c_j|^2 - 2 c_s.c_j, 1e-6)), value (dist + 100 I + 1e-6)^-1 into
-// v[3], its gradient w.r.t. c_s through both the (s, j) and (j, s) entries into v[0..2].
-// c: the pre-step centres [M][3] (raw = activated).
-__device__ __forceinline__ void repulsion_row(const float* c, int M, int s, int j0, int stride, float (&v)[4]) {
-#pragma clang fp contract(off)
-  const float cx = c[3 * s], cy = c[3 * s + 1], cz = c[3 * s + 2];
-  const float csq = cx * cx + cy * cy + cz * cz;
-  for (int j = j0; j < M; j += stride) {
-    const float ox = c[3 * j], oy = c[3 * j + 1], oz = c[3 * j + 2];
-    const float q = (csq + (ox * ox + oy * oy + oz * oz)) - (cx * ox + cy * oy + cz * oz) * 2.0f;
-    const float qc = fmaxf(q, 1e-6f);
-    const float rho = sqrtf(qc);
-    const float den = rho + (j == s ? 100.0f : 0.0f) + 1e-6f;
-    const float inv = frcp(den);  // v_rcp / v_rsq (1 ulp) instead of IEEE divisions: O(M^2) pairs
-    v[3] += inv;
-    if (j != s && q >= 1e-6f) {  // clamp_min(1e-6) gate (the diagonal has q ~ 0)
-      const float gs = -2.0f * inv * inv * frsq(qc);
-      v[0] += gs * (cx - ox);
-      v[1] += gs * (cy - oy);
-      v[2] += gs * (cz - oz);
-    }
-  }
-}
-
-// Pass A of the optimizer: block s owns sphere s. It snapshots the sphere's raw parameters
-// (the update kernel reads neighbours' pre-step values) and, with penalties, sums the
-// repulsion row of training.rs:73-82 over j (repulsion_row), block tree reduction.
-__global__ __launch_bounds__(256) void rm_penalty_pairs(const float* __restrict__ raw, int M, int with_pen,
-                                                        float* __restrict__ snap, float* __restrict__ pair) {
-  __shared__ float red[4 * 256];
-  const int s = blockIdx.x;
-  if (threadIdx.x < 7) {
-    const int idx = threadIdx.x < 3 ? 3 * s + threadIdx.x
-                                    : (threadIdx.x < 6 ? 3 * M + 3 * s + (threadIdx.x - 3) : 6 * M + s);
-    snap[idx] = raw[idx];
-  }
-  if (s == 0 && threadIdx.x >= 32 && threadIdx.x < 36) snap[7 * M + threadIdx.x - 32] = raw[7 * M + threadIdx.x - 32];
-  if (!with_pen) return;
-  float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  repulsion_row(raw, M, s, threadIdx.x, 256, v);
-  block_sum4(v, red);
-  if (threadIdx.x < 4) pair[4 * s + threadIdx.x] = v[threadIdx.x];
-}
-
-// One parameter element i of the packed layout: chain rule of the activations, the compute_loss
-// penalties (training.rs:38-82), coupled weight decay and Burn's Adam; optionally the activated
-// parameters of the updated model (scene.rs:41-45) for the next step's render. Contraction is off
-// in these functions (explicit fmaf where a fused multiply-add is meant): the optimizer runs inside
-// several kernels (its own launches, the reduction's and the small kernel's last blocks), and its
-// bits must not depend on which. Split in two: the
-// part that depends on the pre-step parameters only (optimizer_pre: the chain-rule factor, the
-// penalties' gradient terms and loss share -- the fused iteration runs it while the gradient is
-// still being summed) and the update itself (optimizer_apply).
-struct ElemPre {
-  float fac;         // d activation / d raw (1 for centres and light)
-  float t0, t1, t2;  // penalty gradient terms, added in this order after the chain rule
-  float pen;         // the element's penalty-loss share
-};
-// raw: the pre-step parameters (a snapshot: neighbours are read); pair: the repulsion rows.
-__device__ __forceinline__ ElemPre optimizer_pre(int i, const float* raw, const float* pair, int M, int with_pen) {
-#pragma clang fp contract(off)
-  ElemPre e{1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  const float x = raw[i];
-  const float invM = 1.0f / (float)M;
-  const float rep_scale = 1e-5f / ((float)M * (float)M);
-  if (i < 3 * M) {  // centers (identity activation)
-    if (with_pen) {
-      const int s = i / 3, ax = i - 3 * s;
-      const float cx = raw[3 * s], cy = raw[3 * s + 1], cz = raw[3 * s + 2];
-      const float rs = softplusf_(raw[6 * M + s]);  // penalties use softplus without +0.01 (training.rs:41)
-      e.t0 = 0.05f * 2.0f * x / (3.0f * M);         // [b] mean(c^2) over [M,3] * 0.05
-      const float csq = cx * cx + cy * cy + cz * cz;
-      const float dist = sqrtf(csq + 1e-6f);
-      const float reach = dist + rs;                // [c] mean(mask * (|c| + r - 1.2)^2) * 5
-      if (reach > 1.2f) e.t1 = 5.0f * invM * 2.0f * (reach - 1.2f) * (x / dist);
-      e.t2 = rep_scale * pair[4 * s + ax];          // [d] repulsion (repulsion_row)
-      if (ax == 0) {
-        e.pen += 0.05f * csq / (3.0f * M);
-        if (reach > 1.2f) e.pen += 5.0f * invM * (reach - 1.2f) * (reach - 1.2f);
-        e.pen += rep_scale * pair[4 * s + 3];
-      }
-    }
-  } else if (i < 6 * M) {  // colors: d sigmoid = c (1 - c)
-    const float c = sigmoidf_(x);
-    e.fac = c * (1.0f - c);
-  } else if (i < 7 * M) {  // radius: d (softplus + 0.01) = sigmoid
-    const float sg = sigmoidf_(x);
-    e.fac = sg;
-    if (with_pen) {
-      const int s = i - 6 * M;
-      const float rs = softplusf_(x);
-      e.t0 = 0.002f * invM * (rs > 0.0f ? 1.0f : (rs < 0.0f ? -1.0f : 0.0f)) * sg;  // [a] L1
-      e.pen += 0.002f * invM * fabsf(rs);
-      if (rs > 1.0f) {  // [a] large radius
-        e.t1 = 0.04f * invM * 2.0f * rs * sg;
-        e.pen += 0.04f * invM * rs * rs;
-      }
-      const float cx = raw[3 * s], cy = raw[3 * s + 1], cz = raw[3 * s + 2];
-      const float reach = sqrtf(cx * cx + cy * cy + cz * cz + 1e-6f) + rs;
-      if (reach > 1.2f) e.t2 = 5.0f * invM * 2.0f * (reach - 1.2f) * sg;  // [c] w.r.t. radius
-    }
-  } else if (i >= 7 * M + 3) {  // ambient: d sigmoid (light_dir raw: identity)
-    const float a = sigmoidf_(x);
-    e.fac = a * (1.0f - a);
-  }
-  return e;
-}
-
-// Adam's bias corrections 1 - beta^t (Burn Adam: beta1 0.9, beta2 0.999)
-struct AdamBias {
-  float c1, c2;
-};
-__device__ __forceinline__ AdamBias adam_bias(int step) {
-  return AdamBias{1.0f - powf(0.9f, (float)step), 1.0f - powf(0.999f, (float)step)};
-}
-
-// The update of element i from its gradient g w.r.t. the activated value, its pre-step raw value
-// x and moments mo1 / mo2: gv = g fac + t0 + t1 + t2, Burn Adam with coupled weight decay
-// (g += wd theta; moments; bias correction).
-__device__ __forceinline__ void optimizer_apply(int i, const ElemPre& e, float g, float x, float mo1, float mo2,
-                                                const AdamBias& bias, float lr, float wd, int M,
-                                                float* __restrict__ raw_out, float* __restrict__ m1,
-                                                float* __restrict__ m2, float* __restrict__ act_out,
-                                                _Float16* __restrict__ col_h_out) {
-#pragma clang fp contract(off)
-  float gv = ((g * e.fac + e.t0) + e.t1) + e.t2;
-  gv = fmaf(wd, x, gv);
-  const float b1 = 0.9f, b2 = 0.999f, eps = 1e-5f;
-  const float mm = fmaf(b1, mo1, (1.0f - b1) * gv);
-  const float vv = fmaf(b2, mo2, (1.0f - b2) * gv * gv);
-  m1[i] = mm;
-  m2[i] = vv;
-  const float mh = mm / bias.c1;
-  const float vh = vv / bias.c2;
-  const float xn = x - lr * (mh / (sqrtf(vh) + eps));
-  raw_out[i] = xn;
-  if (act_out) act_out[i] = activate_elem(xn, i, M);
-  // fp16 colour models (RM_MARCH_COLOR_F16): the next render's colours, rounded to nearest
-  if (col_h_out != nullptr && i >= 3 * M && i < 6 * M) col_h_out[i - 3 * M] = (_Float16)activate_elem(xn, i, M);
-}
-
-// Both parts for one element; returns the element's penalty-loss share.
-__device__ __forceinline__ float optimizer_elem(int i, const float* raw, float* __restrict__ raw_out,
-                                                const float* __restrict__ gact, const float* m1_in,
-                                                const float* m2_in, float* __restrict__ m1, float* __restrict__ m2,
-                                                const float* pair, int M, int step, float lr, float wd, int with_pen,
-                                                float* __restrict__ act_out, _Float16* __restrict__ col_h_out) {
-  const ElemPre e = optimizer_pre(i, raw, pair, M, with_pen);
-  optimizer_apply(i, e, gact[i], raw[i], m1_in[i], m2_in[i], adam_bias(step), lr, wd, M, raw_out, m1, m2, act_out,
-                  col_h_out);
-  return e.pen;
-}
-
-// Pass B: one thread per parameter element (optimizer_elem); per-block penalty partials.
-__global__ __launch_bounds__(256) void rm_optimizer_kernel(const float* __restrict__ raw, float* __restrict__ raw_out,
-                                                           const float* __restrict__ gact,
-                                                           float* __restrict__ m1, float* __restrict__ m2,
-                                                           const float* __restrict__ pair, int M, int step,
-                                                           float lr, float wd, int with_pen,
-                                                           float* __restrict__ pen_parts,
-                                                           float* __restrict__ act_out,
-                                                           _Float16* __restrict__ col_h_out,
-                                                           const rm_step_scalars* __restrict__ sdev) {
-  __shared__ float red[4 * 256];
-  if (sdev != nullptr) step = sdev->step;  // device step scalars (rm_bind_step_scalars)
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const int n = 7 * M + 4;
-  float pen = 0.0f;
-  if (i < n)
-    pen = optimizer_elem(i, raw, raw_out, gact, m1, m2, m1, m2, pair, M, step, lr, wd, with_pen, act_out, col_h_out);
-  if (pen_parts != nullptr) {
-    float v[4] = {pen, 0.0f, 0.0f, 0.0f};
-    block_sum4(v, red);
-    if (threadIdx.x == 0) pen_parts[blockIdx.x] = v[0];
-  }
-}
-
-// The optimizer step of a small model (M <= kOptSmallMaxM) in one block: the pre-step parameters
-// into LDS (the snapshot rm_penalty_pairs writes), the repulsion rows of training.rs:73-82 (four
-// threads per sphere, their partials added in order), optimizer_pre per element and the penalty
-// sum (block tree reduction) -- everything that does not need the gradient (opt_small_pre) --
-// then optimizer_apply per element (opt_small_post). One launch instead of three.
-// OptPrefetch: the block's loads of the parameters and moments (elements tid and tid + 256),
-// issued before whatever the block does next (the fused iteration's final reduction) so that
-// their latency overlaps it.
-constexpr int kOptSmallMaxM = 64;
-struct OptPrefetch {
-  float x[2], a[2], b[2];
-};
-__device__ __forceinline__ OptPrefetch opt_prefetch(const float* raw, const float* m1, const float* m2, int M) {
-  OptPrefetch f;
-  const int n = 7 * M + 4;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int i = (int)threadIdx.x + 256 * h;
-    f.x[h] = i < n ? raw[i] : 0.0f;
-    f.a[h] = i < n ? m1[i] : 0.0f;
-    f.b[h] = i < n ? m2[i] : 0.0f;
-  }
-  return f;
-}
-struct OptPre {
-  ElemPre e[2];  // elements tid and tid + 256
-  AdamBias bias;
-};
-
-// The gradient-independent part, for a 256-thread block (every thread calls it: block barriers).
-__device__ __forceinline__ OptPre opt_small_pre(const OptPrefetch& pf, int M, int step, int with_pen,
-                                                float* __restrict__ loss_penalty) {
-  static_assert(7 * kOptSmallMaxM + 4 <= 512, "two elements per thread");
-  __shared__ float snap[7 * kOptSmallMaxM + 4];
-  __shared__ float part[4][kOptSmallMaxM][4];
-  __shared__ float pair[kOptSmallMaxM * 4];
-  __shared__ float red[4 * 256];
-  const int tid = threadIdx.x;
-  const int n = 7 * M + 4;
-  OptPre o;
-  o.bias = adam_bias(step);
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int i = tid + 256 * h;
-    if (i < n) snap[i] = pf.x[h];
-  }
-  __syncthreads();
-  if (with_pen) {
-    const int s = tid >> 2, k = tid & 3;  // sphere s, columns j = k mod 4
-    if (s < M) {
-      float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      repulsion_row(snap, M, s, k, 4, v);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) part[k][s][c] = v[c];
-    }
-    __syncthreads();
-    if (tid < 4 * M) {
-      const int s2 = tid >> 2, c = tid & 3;
-      pair[4 * s2 + c] = ((part[0][s2][c] + part[1][s2][c]) + part[2][s2][c]) + part[3][s2][c];
-    }
-    __syncthreads();
-  }
-  float pen = 0.0f;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int i = tid + 256 * h;
-    o.e[h] = i < n ? optimizer_pre(i, snap, pair, M, with_pen) : ElemPre{1.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    pen += o.e[h].pen;
-  }
-  if (loss_penalty != nullptr) {
-    float v[4] = {pen, 0.0f, 0.0f, 0.0f};
-    block_sum4(v, red);
-    if (tid == 0) loss_penalty[0] = v[0];
-  }
-  return o;
-}
-
-// The update on the gradient g (w.r.t. the activated values) of elements tid and tid + 256.
-__device__ __forceinline__ void opt_small_post(const OptPre& o, const OptPrefetch& pf, const float (&g)[2],
-                                               float* __restrict__ raw, float* __restrict__ m1,
-                                               float* __restrict__ m2, int M, float lr, float wd,
-                                               float* __restrict__ act_out, _Float16* __restrict__ col_h_out) {
-  const int n = 7 * M + 4;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int i = (int)threadIdx.x + 256 * h;
-    if (i < n)
-      optimizer_apply(i, o.e[h], g[h], pf.x[h], pf.a[h], pf.b[h], o.bias, lr, wd, M, raw, m1, m2, act_out,
-                      col_h_out);
-  }
-}
-
-__global__ __launch_bounds__(256) void rm_optimizer_small(float* __restrict__ raw, const float* __restrict__ gact,
-                                                          float* __restrict__ m1, float* __restrict__ m2, int M,
-                                                          int step, float lr, float wd, int with_pen,
-                                                          float* __restrict__ loss_penalty, float* __restrict__ act_out,
-                                                          _Float16* __restrict__ col_h_out,
-                                                          rm_step_scalars* __restrict__ sdev) {
-  const OptPrefetch pf = opt_prefetch(raw, m1, m2, M);
-  if (sdev != nullptr) step = sdev->step;  // device step scalars (rm_bind_step_scalars)
-  const int n = 7 * M + 4, i0 = (int)threadIdx.x;
-  const float g[2] = {i0 < n ? gact[i0] : 0.0f, i0 + 256 < n ? gact[i0 + 256] : 0.0f};
-  const OptPre o = opt_small_pre(pf, M, step, with_pen, loss_penalty);
-  opt_small_post(o, pf, g, raw, m1, m2, M, lr, wd, act_out, col_h_out);
-  if (sdev != nullptr) {  // every thread has read the step: the training step ends here
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      sdev->step += 1;
-      sdev->index += 1;
-    }
-  }
-}
-
-// rm_optimizer_small's step inside the gradient reduction's last block (rm_reduce_partials,
-// FinalArgs::raw): the same functions on the same values -- the gradient read with agent-scope
-// loads after the hand-off -- so the same bits as the separate launch.
-__device__ void fused_optimizer(const FinalArgs& f, int M) {
-  const OptPrefetch pf = opt_prefetch(f.raw, f.m1, f.m2, M);
-  const int step = f.sdev != nullptr ? f.sdev->step : f.step;
-  const int n = 7 * M + 4, i0 = (int)threadIdx.x;
-  float g[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int i = i0 + 256 * h;
-    g[h] = i < n ? __hip_atomic_load(f.gc + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0f;
-  }
-  const OptPre o = opt_small_pre(pf, M, step, f.with_pen, f.loss_penalty);
-  opt_small_post(o, pf, g, f.raw, f.m1, f.m2, M, f.lr, f.wd, f.act_out, f.col_h);
-  if (f.sdev != nullptr) {  // every thread has read the step: the training step ends here
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      f.sdev->step += 1;
-      f.sdev->index += 1;
-    }
-  }
-}
-
-// The end of a training step with device step scalars bound (multi-block optimizer path).
-__global__ void rm_step_advance(rm_step_scalars* sdev) {
-  if (threadIdx.x == 0) {
-    sdev->step += 1;
-    sdev->index += 1;
-  }
-}
-
-__global__ void rm_sum_small(const float* __restrict__ parts, int n, float* __restrict__ out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    float acc = 0.0f;
-    for (int i = 0; i < n; ++i) acc += parts[i];
-    out[0] = acc;
-  }
-}
-
+#include "rm_reduce.h"
 #include "rm_small.h"
 #include "rm_raygrad.h"
 
@@ -3905,19 +2758,6 @@ int ensure_block_order(rm_context* ctx, int tx, int ty, int sub) {
     return dx * dx + dy * dy;
   };
   std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return key(x) < key(y); });
-  if (const char* e = std::getenv("RM_ORDER_EXPERIMENT")) {  // A/B of dispatch orders (timing only)
-    const int mode = std::atoi(e);
-    if (mode == 1) std::reverse(ord.begin(), ord.end());  // border tiles first
-    if (mode == 2) {  // alternate centre and border: heavy and light blocks interleaved
-      std::vector<int> o2;
-      size_t lo = 0, hi = ord.size();
-      while (lo < hi) {
-        o2.push_back(ord[lo++]);
-        if (lo < hi) o2.push_back(ord[--hi]);
-      }
-      ord.swap(o2);
-    }
-  }
   if (ctx->block_order) {
     RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
     RM_HIP(ctx, hipFree(ctx->block_order));
@@ -4290,8 +3130,7 @@ int run_small(rm_context* ctx, const Call& c, KArgs& a, long long n) {
     if (c.fused) sa = *c.fused;
     if (has_bwd) sa.fin = final_args(c, first);
     sa.arrivals = ctx->arrivals;
-    sa.final_in_kernel = has_bwd && nb <= kSmallFinalMaxBlocks && !env_is("RM_SMALL_FINAL", '0') ? 1 : 0;
-    sa.acquire = env_is("RM_SMALL_ACQUIRE", '0') ? 0 : 1;
+    sa.final_in_kernel = has_bwd && nb <= kSmallFinalMaxBlocks ? 1 : 0;
     if (c.fused && (!sa.final_in_kernel || nr != n))  // rm_train_iteration / _step_sampled checked this
       return fail(ctx, RM_ERR_INVALID_ARG, "fused iteration needs one launch of <= %d blocks", kSmallFinalMaxBlocks);
     const bool extra = c.fused && sa.adam;  // the launch's extra (optimizer) block
@@ -4482,9 +3321,8 @@ int run(rm_context* ctx, const Call& c) {
       split = (M >= kSplitMinSpheres && n_all <= kSplitMaxRays) || (M >= kSplitMinSpheresWide && n_all <= kSplitMaxRaysWide);
   }
   a.split = split ? 1 : 0;
-  // ray mode in every split launch (the scene-uniform shift, per-ray retirement and the ray-level
-  // continuation; the split kernels are compiled for it, KArgs::ray_mode)
-  a.ray_mode = split ? 1 : 0;
+  // every split launch runs in ray mode (the scene-uniform shift, per-ray retirement and the
+  // ray-level continuation: the split kernels are compiled for it, see KArgs::cont_cap)
   const int rpb = split ? kSplitRays : kBlock;  // rays per block
   a.cull = ((c.march->flags & RM_MARCH_SKIP_ESCAPED) != 0 && mask_vanishes && !c.t_out && !c.dbg && !split) ? 1 : 0;
   a.cull_min_d = c.mode == kRender ? 50.0f : std::max(50.0f, 160.0f / (a.msharp * 1.44269504f));
@@ -4641,29 +3479,25 @@ int run(rm_context* ctx, const Call& c) {
       a.btrace = ctx->btrace;
       ctx->btrace_waves = nb * kWaves;
 #endif
-      // Split continuation (bwd / train launches with the early exit): the blocks still marching
-      // at step cont_steps stop there, and a second launch runs just those from their saved
-      // state, dispatched one after another at its front -- spread evenly over the CUs, where the
-      // first launch placed them by a cost order that only partly predicts which 64-ray groups
-      // march every step. Bit-identical to one launch (tests/test_gpu_split.py).
-      // continuations at increasing steps (split_cont_caps): launch k resumes the blocks the
-      // previous launch deferred (list k % 2) and defers, at the next step of the list, into list
-      // (k + 1) % 2, whose counts are cleared before it runs
+      // Split continuation (bwd / train launches with the early exit; KArgs::cont_cap): the groups
+      // whose rays still march at step caps[0] stop there and list themselves and those rays;
+      // continuation launches at increasing steps (split_cont_caps) march the listed rays packed
+      // into full blocks -- spread evenly over the CUs, where the first launch placed the groups by
+      // a cost order that only partly predicts which of them march every step -- and a resume
+      // launch finishes the listed groups. Bit-identical to one launch (tests/test_gpu_split.py).
       int caps[kMaxCont + 1];
       const int ncaps = split_cont_caps(a.steps, caps);
       const bool cont = split && c.mode != kRender && c.mode != kFwd && a.early_exit && ncaps > 0 &&
                         a.steps >= 2 * caps[0];
-      int* lists[2] = {nullptr, nullptr};
-      int* counts[2] = {nullptr, nullptr};
-      const bool rmode = cont && a.ray_mode;
+      int* glist = nullptr;   // the deferred groups and their count
+      int* gcount = nullptr;
       int* rlists[2] = {nullptr, nullptr};
       int* rcounts[2] = {nullptr, nullptr};
       if (cont) {
         const long long rays = nb * kSplitRays;
-        // per ray: 7 state rows (8 in ray mode), per group 2 words; the group lists; ray mode: two
-        // ray lists of up to `rays` entries and their counts
-        const size_t need = (size_t)(8 * rays + 2 * nb) * sizeof(float) +
-                            (size_t)(2 * kContClasses * nb + 2 * kContClasses + 16) * sizeof(int) +
+        // per ray 8 state rows, per group 2 words (KArgs::cont_state); the group list and its count;
+        // two ray lists of up to `rays` entries and their counts
+        const size_t need = (size_t)(8 * rays + 2 * nb) * sizeof(float) + (size_t)(nb + 8 + 16) * sizeof(int) +
                             (size_t)(2 * rays + 16) * sizeof(int);
         if (ctx->cont_bytes < need) {
           if (ctx->cont_buf) RM_HIP(ctx, hipFree(ctx->cont_buf));
@@ -4672,38 +3506,31 @@ int run(rm_context* ctx, const Call& c) {
           RM_HIP(ctx, hipMalloc(&ctx->cont_buf, need));
           ctx->cont_bytes = need;
         }
-        lists[0] = reinterpret_cast<int*>(ctx->cont_buf + 8 * rays + 2 * nb);
-        lists[1] = lists[0] + kContClasses * nb;
-        counts[0] = lists[1] + kContClasses * nb;
-        counts[1] = counts[0] + kContClasses;
-        rcounts[0] = counts[1] + kContClasses;
-        rcounts[1] = rcounts[0] + 8;  // a 32-byte line each
+        glist = reinterpret_cast<int*>(ctx->cont_buf + 8 * rays + 2 * nb);
+        gcount = glist + nb;
+        rcounts[0] = gcount + 8;  // the three counts 32 bytes apart
+        rcounts[1] = rcounts[0] + 8;
         rlists[0] = rcounts[1] + 8;
         rlists[1] = rlists[0] + rays;
         a.cont_state = ctx->cont_buf;
         a.cont_rays = rays;
-        a.cont_list_w = lists[0];
-        a.cont_count_w = counts[0];
+        a.cont_list_w = glist;
+        a.cont_count_w = gcount;
         a.cont_cap = caps[0];
         a.cont_resume = 0;
-        a.cont_stride = (int)nb;
-        a.cont_order = env_is("RM_CONT_ORDER", '0') ? 0 : 1;
-        RM_HIP(ctx, hipMemsetAsync(counts[0], 0, 2 * kContClasses * sizeof(int), ctx->stream));
-        if (rmode) {  // the first launch appends the marching rays to ray list 0
-          a.ray_list_w = rlists[0];
-          a.ray_count_w = rcounts[0];
-          RM_HIP(ctx, hipMemsetAsync(rcounts[0], 0, 16 * sizeof(int), ctx->stream));
-        }
+        a.ray_list_w = rlists[0];  // the first launch appends the marching rays to ray list 0
+        a.ray_count_w = rcounts[0];
+        RM_HIP(ctx, hipMemsetAsync(gcount, 0, (8 + 16) * sizeof(int), ctx->stream));  // the three counts
       }
       if (c.mode == kFwd) launch_ray<kFwd>(c.cam, split, grid, lds, ctx->stream, a, ev0, ev1);
       else if (c.mode == kBwd) launch_ray<kBwd>(c.cam, split, grid, lds, ctx->stream, a, ev0, ev1);
       else if (c.mode == kTrain) launch_ray<kTrain>(c.cam, split, grid, lds, ctx->stream, a, ev0, ev1);
       else launch_ray<kRender>(c.cam, false, grid, lds, ctx->stream, a, ev0, ev1);
       RM_HIP(ctx, hipGetLastError());
-      // ray mode: continuation k marches the rays of ray list k % 2 (deferring at the next cap into
+      // continuation k marches the rays of ray list k % 2 (deferring at the next cap into
       // list (k + 1) % 2, whose count is cleared first: continuation k - 1 read it), then one resume
       // launch runs the deferred groups' post-march forward and backward from their final states
-      for (int ph = 0; rmode && ph < ncaps; ++ph) {
+      for (int ph = 0; cont && ph < ncaps; ++ph) {
         KArgs b = a;
         b.ray_cont = 1;
         b.cont_resume = caps[ph];
@@ -4726,12 +3553,12 @@ int run(rm_context* ctx, const Call& c) {
         else launch_cont<kTrain>(c.cam, grid, lds, ctx->stream, b, e0, e1);
         RM_HIP(ctx, hipGetLastError());
       }
-      if (rmode) {
+      if (cont) {
         KArgs b = a;
         b.cont_resume = a.steps;
         b.cont_cap = 0;
-        b.cont_list = lists[0];
-        b.cont_count = counts[0];
+        b.cont_list = glist;
+        b.cont_count = gcount;
         b.cont_list_w = nullptr;
         b.cont_count_w = nullptr;
         b.ray_list_w = nullptr;
@@ -4891,13 +3718,6 @@ int rm_stats_collect(rm_context* ctx, rm_stats* out, int32_t reset) {
   out->steps_saved = (int64_t)v[2];
   out->seeded_rays = (int64_t)v[4];
   out->seeded_rays_a = (int64_t)v[5];
-#ifdef RM_LANE_STATS
-  std::fprintf(stderr, "RM_LANE_STATS escaped_lane_sweeps %llu\n", v[3]);
-#endif
-#ifdef RM_RAY_STATS
-  std::fprintf(stderr, "RM_RAY_STATS needed_lane_steps %llu waves %lld steps_saved %llu after_cap_run %llu "
-               "after_cap_packed %llu\n", v[3], (long long)ctx->stats_waves, v[2], v[6], v[7]);
-#endif
   if (reset) {
     RM_HIP(ctx, hipMemsetAsync(ctx->stats_dev, 0, sizeof v, ctx->stream));
     ctx->stats_blocks = 0;
@@ -5397,8 +4217,7 @@ int check_sampling(rm_context* ctx, const float* ray_org, const float* ray_dir, 
 bool sampled_one_launch(const Call& c, int M, long long n) {
   const int rpb = kBlock / small_lpr(c, n);
   return use_small(c, M, n) && (n + rpb - 1) / rpb <= kSmallFinalMaxBlocks &&
-         (n + rpb - 1) / rpb <= max_blocks_per_launch() && !env_is("RM_SMALL_FINAL", '0') &&
-         !env_is("RM_FUSED_ITER", '0');
+         (n + rpb - 1) / rpb <= max_blocks_per_launch() && !env_is("RM_FUSED_ITER", '0');
 }
 
 }  // namespace

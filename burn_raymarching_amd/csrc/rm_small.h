@@ -41,7 +41,6 @@ struct SmallArgs {
   FinalArgs fin;          // where the last block writes the gradients and the loss
   unsigned* arrivals;     // arrival counter (zero between launches; the last block resets it)
   int final_in_kernel;    // 1: the last block reduces and finalizes; 0: partial records only
-  int acquire;            // 1: the last block runs an agent-scope acquire before its loads
   // The fused training iteration (rm_train_iteration; kernel template FUSED): the batch is drawn
   // and gathered in the kernel (rm_sample_kernel's rows: ray i of the call reads row j of the
   // dataset arrays) and the last block runs the optimizer step on the gradient it has summed.
@@ -174,9 +173,9 @@ __device__ __forceinline__ void small_final(const KArgs& a, const SmallArgs& sa,
   // each storing wave drained (vmcnt(0)) before the barrier behind which one lane adds to the one
   // counter whose last add tells this block: the hand-off row of MI355X_MICROARCH.md
   // (inter-workgroup visibility) under which sc1 loads may replace the agent-scope acquire. The
-  // acquire is kept (sa.acquire, env RM_SMALL_ACQUIRE=0 drops it): without it the tail measured
-  // the same (tools/small_trace.py: 4.96 vs 5.12 us at 128 blocks).
-  if (sa.acquire && tid == 0) {
+  // acquire is kept, unconditionally: without it the tail measured the same (tools/small_trace.py:
+  // 4.96 vs 5.12 us at 128 blocks), so dropping it would buy nothing for a weaker guarantee.
+  if (tid == 0) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }

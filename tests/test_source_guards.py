@@ -47,14 +47,15 @@ def _body(src, signature):
     "__device__ __forceinline__ void optimizer_apply(",
 ])
 def test_trajectory_helpers_compile_without_contraction(signature):
-    body = _body(_src("rm_kernels.hip"), signature)
+    # the helpers live in rm_kernels.hip and in the headers it includes (one translation unit)
+    body = _body(_src("rm_kernels.hip") + _src("rm_reduce.h"), signature)
     first = body.split("\n", 2)[1].strip()
     assert first == "#pragma clang fp contract(off)", f"{signature} must open with contraction off"
 
 
 def test_light_direction_gradient_has_one_definition():
     """Every light-direction gradient is light_grad's: no kernel forms (r - ln proj) / len itself."""
-    for name in ("rm_kernels.hip", "rm_small.h"):
+    for name in ("rm_kernels.hip", "rm_reduce.h", "rm_small.h"):
         src = _src(name)
         # the Jacobian of l / |l| written out anywhere but in light_grad
         body = _body(src, "__device__ __forceinline__ float light_grad(") if "float light_grad(" in src else ""
