@@ -1,6 +1,9 @@
 """Build recipe for the in-tree native libraries (hipcc for gfx950; no JIT cache).
 
-  burn_raymarching_amd/lib/libraymarch_hip.so  <- csrc/rm_kernels.hip   (the product: C ABI of include/raymarch.h)
+  burn_raymarching_amd/lib/libraymarch_hip.so  <- csrc/rm_kernels.hip   (the product: C ABI of include/raymarch.h;
+                                                  one translation unit: the kernels in rm_kernels.hip and
+                                                  rm_{device,reduce,small,raygrad}.h, the host side in
+                                                  rm_{context,launch,api}.h)
   burn_raymarching_amd/lib/librm_host.so        <- csrc/host/{io,data,driver,comm}.cpp (C ABI of include/rm_host.h; RCCL)
   burn_raymarching_amd/lib/rm_train             <- csrc/host/main.cpp    (CLI: train / generate / preview)
 
@@ -42,7 +45,8 @@ def _stale(target: str, sources) -> bool:
 # shipped .so names the source it came from (tests/test_abi.py compares it with the tree).
 KERNEL_SOURCES = [os.path.join(CSRC, "rm_kernels.hip"), os.path.join(CSRC, "rm_device.h"),
                   os.path.join(CSRC, "rm_reduce.h"), os.path.join(CSRC, "rm_small.h"),
-                  os.path.join(CSRC, "rm_raygrad.h"),
+                  os.path.join(CSRC, "rm_raygrad.h"), os.path.join(CSRC, "rm_context.h"),
+                  os.path.join(CSRC, "rm_launch.h"), os.path.join(CSRC, "rm_api.h"),
                   os.path.join(ROOT, "include", "raymarch.h")]
 
 

@@ -2663,1940 +2663,9 @@ __global__ __launch_bounds__(64) void rm_stall_kernel(const int* flag, unsigned 
 }  // namespace rm
 
 // =======================================================================================
-// C ABI
+// Host side (one translation unit): the context and its device buffers, the launch
+// orchestration, and the C ABI of include/raymarch.h
 // =======================================================================================
-struct rm_context {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  rm_step_scalars* sdev = nullptr;  // device step scalars (rm_bind_step_scalars), nullable
-  std::string err;
-  void* ws = nullptr;  // partials | segment sums | small scratch
-  size_t ws_bytes = 0;
-  float* rg_ws = nullptr;  // ray-gradient calls: march t [rays] | per-view partial rows (rm_raygrad_kernel)
-  size_t rg_bytes = 0;
-  bool timing = false;  // record hipEvents around every per-ray kernel launch
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
-  size_t events_used = 0;
-  unsigned long long* stats_dev = nullptr;  // work counters (rm_stats_enable), kStatsWords words
-  int* esc_flags = nullptr;                 // per-block escape flags, kMaxBlocksPerLaunch ints
-  void* rec = nullptr;                      // sphere records of the current call (rm_prep_kernel)
-  unsigned* arrivals = nullptr;             // rm_small_kernel's arrival counter (zero between launches)
-  unsigned* red_arrivals = nullptr;         // rm_reduce_partials' per-column-block arrival counters
-  rm::CamBasis* cams_dev = nullptr;         // camera bases of calls with > kInlineCams views (device)
-  rm::CamBasis* cams_pin = nullptr;         // their pinned host staging, kCamRing slots
-  hipEvent_t cam_ev[32] = {};               // slot k's copy has run (kCamRing slots)
-  int cam_slot = 0;
-  std::vector<rm::CamBasis> cams_shadow;    // what the device table holds (the last upload)
-  float* batch = nullptr;                   // rm_train_iteration's unfused path: the drawn batch (9 floats/ray)
-  float* opt_pre = nullptr;                 // rm_train_iteration: the optimizer part of the launch's extra block
-  // rm_train_step_sampled_prepared: opt_pre holds the next rm_optimizer_step's gradient-independent
-  // part for these arguments (consumed by that call, cleared by any other use of opt_pre)
-  bool opt_prepared = false;
-  const float* prep_raw = nullptr;
-  float* prep_loss_penalty = nullptr;
-  int prep_M = 0, prep_step = 0, prep_pen = 0;
-  unsigned* opt_arrival = nullptr;          // rm_train_step_camera_adam: the reduction's column-block counter
-  bool adam_done = false;                   // the last call's optimizer ran inside its reduction
-  size_t batch_bytes = 0;
-  size_t rec_bytes = 0;
-  long long stats_blocks = 0;               // ray blocks launched while stats are on
-  long long stats_waves = 0;                // their ray waves (a split block holds one)
-  int* block_order = nullptr;               // centre-out tile order for order_tx x order_ty tiles
-  int order_tx = 0, order_ty = 0, order_sub = 0;
-  int* olist = nullptr;                     // cost-ordered dispatch: 3 x [class][kMaxBlocksPerLaunch] block lists
-  int* ocnt = nullptr;                      // 3 x [class] list lengths (zeroed one launch ahead)
-  float* cont_buf = nullptr;                // split continuation: saved march state | list | count
-  int* stall_flag = nullptr;                // rm_debug_stall: host-mapped release flag (host pointer)
-  size_t cont_bytes = 0;
-  int* oturn = nullptr;                     // device word: the list set the next keyed launch appends to
-  unsigned long long cost_key = 0;          // geometry of the last keyed launch (its lists order the next)
-  bool cost_valid = false;
-#ifdef RM_BLOCK_TRACE
-  unsigned long long* btrace = nullptr;     // measurement build: per-wave records of the last launch
-  long long btrace_waves = 0;
-#endif
-};
-
-namespace {
-
-using namespace rm;
-
-int fail(rm_context* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-int fail(rm_context* ctx, int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  if (ctx) ctx->err = buf;
-  return code;
-}
-
-#define RM_HIP(ctx, call)                                                                        \
-  do {                                                                                           \
-    hipError_t e_ = (call);                                                                      \
-    if (e_ != hipSuccess) return fail(ctx, RM_ERR_HIP, "%s: %s", #call, hipGetErrorString(e_)); \
-  } while (0)
-
-// Centre-out dispatch order of the ray blocks of a view's tx x ty 16x16 tiles (ray_block): by
-// distance of the block's pixel-centre from the image centre, ties by block index. A block is a
-// whole tile (256-ray blocks) or one of its four 8x8 quadrants (64-ray blocks: the split march), in
-// the pixel order of setup_ray. Built once per image size.
-int ensure_block_order(rm_context* ctx, int tx, int ty, int sub) {
-  if (ctx->block_order && ctx->order_tx == tx && ctx->order_ty == ty && ctx->order_sub == sub) return RM_OK;
-  // sub = ray blocks per 16x16 tile: 1 (256-ray blocks), 4 (8x8 quadrants: 64-ray split blocks),
-  // 8 (8x4 halves of the quadrants: 32-ray split blocks) or 16 (8x2 quarters: 16-ray split blocks)
-  std::vector<int> ord((size_t)tx * ty * sub);
-  for (size_t i = 0; i < ord.size(); ++i) ord[i] = (int)i;
-  auto key = [&](int i) {  // twice the pixel offset of the block centre from the image centre
-    const int tile = i / sub, q = i % sub;
-    const int per_quad = sub / 4, quad = sub == 1 ? 0 : q / per_quad, part = sub == 1 ? 0 : q % per_quad;
-    const long long rows = sub == 1 ? 16 : 8 / per_quad;  // pixel rows of one block inside its quadrant
-    const long long ox = sub == 1 ? 16 : 16 * (quad & 1) + 8,
-                    oy = sub == 1 ? 16 : 16 * (quad >> 1) + 2 * rows * part + rows;
-    const long long dx = 32LL * (tile % tx) + ox - 16LL * tx, dy = 32LL * (tile / tx) + oy - 16LL * ty;
-    return dx * dx + dy * dy;
-  };
-  std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return key(x) < key(y); });
-  if (ctx->block_order) {
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RM_HIP(ctx, hipFree(ctx->block_order));
-    ctx->block_order = nullptr;
-  }
-  RM_HIP(ctx, hipMalloc(&ctx->block_order, sizeof(int) * ord.size()));
-  RM_HIP(ctx, hipMemcpy(ctx->block_order, ord.data(), sizeof(int) * ord.size(), hipMemcpyHostToDevice));
-  ctx->order_tx = tx;
-  ctx->order_ty = ty;
-  ctx->order_sub = sub;
-  return RM_OK;
-}
-
-bool env_is(const char* name, char v) {
-  const char* e = std::getenv(name);
-  return e && e[0] == v;
-}
-
-int pad_spheres(int M) { return (M + kSphereAlign - 1) / kSphereAlign * kSphereAlign; }
-// column blocks of the reduction at the largest scene (RM_MAX_SPHERES): its arrival counters
-constexpr int kRedArrivals = (RM_MAX_SPHERES * 8 + 8 + 255) / 256 * RM_RED_ARR_STRIDE;
-
-// Ray blocks per per-ray launch: kMaxBlocksPerLaunch, or less with the environment variable
-// RM_MAX_BLOCKS_PER_LAUNCH (tests use it to exercise the sub-launch split at small sizes).
-long long max_blocks_per_launch() {
-  const char* e = std::getenv("RM_MAX_BLOCKS_PER_LAUNCH");
-  const long long v = e ? std::atoll(e) : 0;
-  return (v >= 1 && v <= kMaxBlocksPerLaunch) ? v : kMaxBlocksPerLaunch;
-}
-
-long long rec_floats(int Mpad) { return (long long)Mpad * 8 + 8; }
-
-// March steps after which a split launch hands the blocks still marching to a continuation
-// launch: env RM_SPLIT_CONT_STEPS (0 = one launch), else max(32, 3 S / 8) for S >= 64 march steps
-// (measured, tools/gpu_env_ab.sh: at 4096 spheres S = 128 step 48 gave -20 %, S = 64 step 32 -8 %;
-// at S = 32 any step was slower).
-int split_cont_steps(int steps) {
-  if (const char* e = std::getenv("RM_SPLIT_CONT_STEPS")) return std::max(0, std::atoi(e));
-  return steps >= 64 ? std::max(32, 3 * steps / 8) : 0;
-}
-// The second continuation (a third launch) from S >= 128: at 3S/4 the blocks still marching are
-// dealt out again over the CUs (C5 / C5g with 32-ray groups, three rounds on one box: +2.5 % /
-// +3.5 % at 96 of 128 steps, profiles/r06_ab.txt r06r). 0 = none; env RM_SPLIT_CONT2_STEPS.
-int split_cont2_steps(int steps) {
-  if (const char* e = std::getenv("RM_SPLIT_CONT2_STEPS")) return std::max(0, std::atoi(e));
-  return steps >= 128 ? 3 * steps / 4 : 0;
-}
-// The continuation steps of a split launch, increasing, each < steps: caps[0..n), caps[n] = 0.
-// Env RM_SPLIT_CONT_LIST="48,80,112" replaces the rule (up to kMaxCont steps).
-constexpr int kMaxCont = 4;
-int split_cont_caps(int steps, int (&caps)[kMaxCont + 1]) {
-  int n = 0;
-  if (const char* e = std::getenv("RM_SPLIT_CONT_LIST")) {
-    for (const char* q = e; *q && n < kMaxCont;) {
-      const int v = std::atoi(q);
-      if (v > 0 && v < steps && (n == 0 || v > caps[n - 1])) caps[n++] = v;
-      while (*q && *q != ',') ++q;
-      if (*q == ',') ++q;
-    }
-  } else if (steps >= 128 && !std::getenv("RM_SPLIT_CONT_STEPS") && !std::getenv("RM_SPLIT_CONT2_STEPS")) {
-    // ray mode: a continuation costs only the rays still marching, so defer earlier and more
-    // often -- 3S/16, 3S/8, 3S/4 (C5g, one box: 24 / 48 / 96 of 128 steps 42.3 Mrays/s against 39.8
-    // with 48 / 96 and 40.1 with 32 / 96; 16 / 32 / 64 / 96 42.3; C5 within 1 %, profiles/r07g)
-    caps[n++] = 3 * steps / 16;
-    caps[n++] = 3 * steps / 8;
-    caps[n++] = 3 * steps / 4;
-  } else {
-    const int c0 = split_cont_steps(steps), c1 = split_cont2_steps(steps);
-    if (c0 > 0 && c0 < steps) {
-      caps[n++] = c0;
-      if (c1 > c0 && c1 < steps) caps[n++] = c1;
-    }
-  }
-  for (int i = n; i <= kMaxCont; ++i) caps[i] = 0;
-  return n;
-}
-
-size_t ws_need(long long max_rays, int M, int rays_per_block = kBlock) {
-  const int Mpad = pad_spheres(M);
-  long long blocks = (max_rays + rays_per_block - 1) / rays_per_block;
-  blocks = std::min<long long>(blocks, kMaxBlocksPerLaunch);
-  const long long rec = rec_floats(Mpad);
-  return (size_t)(blocks * rec + (long long)reduce_segs(blocks) * rec + 4096) * sizeof(float);
-}
-
-int ensure_ws(rm_context* ctx, size_t bytes) {
-  if (ctx->ws_bytes >= bytes) return RM_OK;
-  if (ctx->ws) {
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RM_HIP(ctx, hipFree(ctx->ws));
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
-  }
-  hipError_t e = hipMalloc(&ctx->ws, bytes);
-  if (e != hipSuccess) {
-    ctx->ws = nullptr;
-    return fail(ctx, RM_ERR_OOM, "workspace allocation of %zu bytes failed: %s", bytes, hipGetErrorString(e));
-  }
-  ctx->ws_bytes = bytes;
-  return RM_OK;
-}
-
-// Workspace of the ray-gradient calls (rm_render_diff_backward_rays / _cameras): the replayed
-// march's t for every ray, then one partial row per 256-ray block of every view.
-size_t rg_need(long long rays) {
-  const long long rows = (rays + kBlock - 1) / kBlock + RM_MAX_VIEWS_PER_CALL;
-  return (size_t)(rays + rows * kRgCols + 64) * sizeof(float);
-}
-
-int ensure_rg(rm_context* ctx, size_t bytes) {
-  if (ctx->rg_bytes >= bytes) return RM_OK;
-  if (ctx->rg_ws) {
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RM_HIP(ctx, hipFree(ctx->rg_ws));
-    ctx->rg_ws = nullptr;
-    ctx->rg_bytes = 0;
-  }
-  if (hipMalloc(&ctx->rg_ws, bytes) != hipSuccess) {
-    ctx->rg_ws = nullptr;
-    return fail(ctx, RM_ERR_OOM, "ray-gradient workspace allocation of %zu bytes failed", bytes);
-  }
-  ctx->rg_bytes = bytes;
-  return RM_OK;
-}
-
-// camera.rs:40-52 on the host, in f32 like the reference.
-int make_basis(rm_context* ctx, const rm_camera& c, int W, int H, CamBasis& b) {
-  auto normalize = [](const float v[3], float out[3]) {
-    const float len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-    if (len == 0.0f) {
-      out[0] = out[1] = out[2] = 0.0f;
-    } else {
-      out[0] = v[0] / len;
-      out[1] = v[1] / len;
-      out[2] = v[2] / len;
-    }
-  };
-  auto cross = [](const float a[3], const float bb[3], float out[3]) {
-    out[0] = a[1] * bb[2] - a[2] * bb[1];
-    out[1] = a[2] * bb[0] - a[0] * bb[2];
-    out[2] = a[0] * bb[1] - a[1] * bb[0];
-  };
-  const float up_w[3] = {0.0f, 1.0f, 0.0f};
-  const float fr[3] = {c.target[0] - c.eye[0], c.target[1] - c.eye[1], c.target[2] - c.eye[2]};
-  float rr[3];
-  normalize(fr, b.fwd);
-  cross(b.fwd, up_w, rr);
-  normalize(rr, b.right);
-  cross(b.right, b.fwd, b.up);
-  const float aspect = (float)W / (float)H;
-  const float rads_per_deg = 3.14159265358979323846f / 180.0f;
-  const float theta = c.fov_deg * rads_per_deg / 2.0f;
-  b.half_h = std::tan(theta);
-  b.half_w = aspect * b.half_h;
-  for (int i = 0; i < 3; ++i) b.eye[i] = c.eye[i];
-  if (!std::isfinite(b.half_h) || !(c.fov_deg > 0.0f && c.fov_deg < 180.0f))
-    return fail(ctx, RM_ERR_INVALID_ARG, "camera fov_deg %g out of (0, 180)", (double)c.fov_deg);
-  return RM_OK;
-}
-
-int check_scene(rm_context* ctx, const rm_scene* s, bool need_light) {
-  if (!s) return fail(ctx, RM_ERR_INVALID_ARG, "scene is NULL");
-  if (s->num_spheres < 1 || s->num_spheres > RM_MAX_SPHERES)
-    return fail(ctx, RM_ERR_INVALID_ARG, "num_spheres %d out of [1, %d]", s->num_spheres, RM_MAX_SPHERES);
-  if (!s->centers || !s->colors || !s->radius || (need_light && (!s->light_dir || !s->ambient)))
-    return fail(ctx, RM_ERR_INVALID_ARG, "scene has a NULL parameter pointer");
-  return RM_OK;
-}
-
-int check_march(rm_context* ctx, const rm_march* m) {
-  if (!m) return fail(ctx, RM_ERR_INVALID_ARG, "march is NULL");
-  if (m->steps < 0 || m->steps > 100000) return fail(ctx, RM_ERR_INVALID_ARG, "steps %d out of range", m->steps);
-  if (!(m->smooth_k > 0.0f) || !std::isfinite(m->smooth_k))
-    return fail(ctx, RM_ERR_INVALID_ARG, "smooth_k must be finite and > 0 (got %g)", (double)m->smooth_k);
-  if (!(m->normal_eps > 0.0f)) return fail(ctx, RM_ERR_INVALID_ARG, "normal_eps must be > 0");
-  return RM_OK;
-}
-
-struct Call {
-  int mode;  // Mode
-  bool cam;
-  const float* org = nullptr;
-  const float* dir = nullptr;
-  long long n = 0;
-  const rm_camera* cams = nullptr;
-  int views = 0, W = 0, H = 0;
-  const rm_scene* scene = nullptr;
-  const rm_march* march = nullptr;
-  float* out = nullptr;
-  float* t_out = nullptr;
-  const float* t_in = nullptr;
-  const float* gout = nullptr;
-  const float* targets = nullptr;
-  float progress = 0.0f, inv_count = 0.0f;
-  float* dbg = nullptr;
-  const rm_grads* grads = nullptr;
-  float* loss_sum = nullptr;
-  int accumulate = 0;
-  // rm_train_iteration: org / dir / targets are the dataset arrays the kernel draws the batch
-  // from, and the optimizer runs in the same launch (rm_small_kernel<kTrain, MB, true>)
-  const SmallArgs* fused = nullptr;
-  // rm_train_step_camera_adam: the optimizer step on the packed gradient (grads->centers), run by
-  // the gradient reduction's last block where it can (rm_context::adam_done says whether it did)
-  struct Adam {
-    float *raw, *m1, *m2, *act_out, *loss_penalty;
-    _Float16* col_h;
-    int step, with_pen;
-    float lr, wd;
-  };
-  const Adam* adam = nullptr;
-};
-
-FinalArgs final_args(const Call& c, bool first) {
-  const rm_grads* gp = c.grads;
-  FinalArgs fa{};
-  fa.light_dir = c.scene->light_dir;
-  fa.gc = gp->centers;
-  fa.gcol = gp->colors;
-  fa.gr = gp->radius;
-  fa.gld = gp->light_dir;
-  fa.gamb = gp->ambient;
-  fa.loss_sum = c.mode == kTrain ? c.loss_sum : nullptr;
-  fa.accumulate = first ? c.accumulate : 1;
-  fa.oturn = nullptr;
-  return fa;
-}
-
-// The fixed-order cross-block reduction of a launch's nb partial records (a.partials) and the
-// gradient scatter into the caller's layout (rm_reduce_partials + rm_finalize_grads).
-int reduce_and_finalize(rm_context* ctx, const Call& c, const KArgs& a, long long nb, bool first, bool only = false) {
-  FinalArgs fa = final_args(c, first);
-  fa.oturn = const_cast<int*>(a.oturn);  // a keyed launch: its reduction advances the turn
-  const int nblocks = (int)nb;
-  const int ncols = a.Mpad * 8 + 8;
-  float* S = a.partials + (long long)std::max<long long>(nb, 1) * a.rec;
-  const int segs = reduce_segs(nblocks);  // every segment is written (empty ones as 0)
-  const int seg_len = (nblocks + segs - 1) / segs;
-  // pass 1 compacts a segment's rows in one 256-entry list (rm_reduce_partials)
-  if (seg_len > 256) return fail(ctx, RM_ERR_INVALID_ARG, "%d ray blocks in one launch", nblocks);
-  const int xblocks = (ncols + 255) / 256;
-  // pass 2 in the same launch (the last-arriving segment block of each column block) unless
-  // RM_REDUCE_FUSED=0 (then rm_finalize_grads: the same bits)
-  const bool fused = !env_is("RM_REDUCE_FUSED", '0');
-  if (fused && !ctx->red_arrivals) {
-    RM_HIP(ctx, hipMalloc(&ctx->red_arrivals, sizeof(unsigned) * kRedArrivals));
-    RM_HIP(ctx, hipMemsetAsync(ctx->red_arrivals, 0, sizeof(unsigned) * kRedArrivals, ctx->stream));
-  }
-  // rm_train_step_camera_adam: the optimizer in the reduction's last block (one launch, the only
-  // one of the call, M <= kOptSmallMaxM, the fused reduction)
-  if (c.adam != nullptr && only && fused && a.M <= kOptSmallMaxM && !env_is("RM_OPT_SMALL", '0') &&
-      !env_is("RM_FUSED_ADAM", '0')) {
-    if (!ctx->opt_arrival) {
-      RM_HIP(ctx, hipMalloc(&ctx->opt_arrival, 128));
-      RM_HIP(ctx, hipMemsetAsync(ctx->opt_arrival, 0, 128, ctx->stream));
-    }
-    fa.raw = c.adam->raw;
-    fa.m1 = c.adam->m1;
-    fa.m2 = c.adam->m2;
-    fa.act_out = c.adam->act_out;
-    fa.loss_penalty = c.adam->loss_penalty;
-    fa.col_h = c.adam->col_h;
-    fa.sdev = ctx->sdev;
-    fa.opt_arrival = ctx->opt_arrival;
-    fa.step = c.adam->step;
-    fa.with_pen = c.adam->with_pen;
-    fa.lr = c.adam->lr;
-    fa.wd = c.adam->wd;
-    ctx->adam_done = true;
-  }
-  hipLaunchKernelGGL(rm_reduce_partials, dim3((unsigned)xblocks, (unsigned)segs), dim3(256), 0, ctx->stream, a.partials,
-                     a.rec, a.M, a.Mpad, nblocks, seg_len, S, fa, fused ? ctx->red_arrivals : nullptr);
-  RM_HIP(ctx, hipGetLastError());
-  if (!fused) {
-    hipLaunchKernelGGL(rm_finalize_grads, dim3((unsigned)((ncols + 63) / 64)), dim3(256), 0, ctx->stream, S, segs, a.M,
-                       a.Mpad, final_args(c, first));
-    RM_HIP(ctx, hipGetLastError());
-  }
-  return RM_OK;
-}
-
-// Per-launch timing events (rm_timing_enable): the next pair of the context's pool.
-int next_events(rm_context* ctx, hipEvent_t& ev0, hipEvent_t& ev1) {
-  ev0 = ev1 = nullptr;
-  if (!ctx->timing) return RM_OK;
-  if (ctx->events_used == ctx->events.size()) {
-    std::pair<hipEvent_t, hipEvent_t> pr;
-    RM_HIP(ctx, hipEventCreate(&pr.first));
-    RM_HIP(ctx, hipEventCreate(&pr.second));
-    ctx->events.push_back(pr);
-  }
-  ev0 = ctx->events[ctx->events_used].first;
-  ev1 = ctx->events[ctx->events_used].second;
-  ++ctx->events_used;
-  return RM_OK;
-}
-
-// Small scenes (M <= kSmallMaxM): rm_small_kernel. Taken by default for ray-array calls (the
-// reference training loop's random batches, train.rs:169-199) and for camera calls of up to
-// kSmallCamMaxRays rays (64x64 / 16 steps: 13.5 vs 56 us, 256x256 / 40 steps: 25 vs 84 us;
-// tools/small_batch_sweep.py -- larger camera calls keep the general kernel's exact early exits);
-// env RM_SMALL=1 takes it for every eligible call, RM_SMALL=0 never. Not for the renderer.rs
-// mode, the diagnostics or the flags that select the general kernel's march paths for testing.
-constexpr long long kSmallCamMaxRays = 1LL << 20;
-bool use_small(const Call& c, int M, long long n) {
-  if (M > kSmallMaxM || n <= 0 || c.mode == kRender || c.dbg) return false;
-  if ((c.march->flags & (RM_MARCH_VALU_ONLY | RM_MARCH_FORCE_MAX_SHIFT | RM_MARCH_SPLIT | RM_MARCH_PER_RAY_ORIGIN |
-                         RM_MARCH_SKIP_ESCAPED)) != 0)
-    return false;
-  const char* e = std::getenv("RM_SMALL");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  return !c.cam || n <= kSmallCamMaxRays;
-}
-
-// rm_small_kernel for M spheres: the bucket of M rounded up to a multiple of 4
-template <int MODE, bool FUSED = false, int LPR = 1>
-void launch_small_m(int M, dim3 grid, hipStream_t st, const KArgs& a, const SmallArgs& sa, hipEvent_t ev0,
-                    hipEvent_t ev1) {
-  const dim3 blk(kBlock);
-  switch ((M + 3) / 4) {
-#define RM_SMALL_CASE(C, MB) \
-  case C: hipExtLaunchKernelGGL((rm_small_kernel<MODE, MB, FUSED, LPR>), grid, blk, 0, st, ev0, ev1, 0u, a, sa); break;
-    RM_SMALL_CASE(1, 4)
-    RM_SMALL_CASE(2, 8)
-    RM_SMALL_CASE(3, 12)
-    RM_SMALL_CASE(4, 16)
-    RM_SMALL_CASE(5, 20)
-    RM_SMALL_CASE(6, 24)
-    RM_SMALL_CASE(7, 28)
-#undef RM_SMALL_CASE
-    default: hipExtLaunchKernelGGL((rm_small_kernel<MODE, 32, FUSED, LPR>), grid, blk, 0, st, ev0, ev1, 0u, a, sa); break;
-  }
-}
-
-// Lanes per ray of a small-kernel call: train steps of up to 32,768 rays split each ray's march
-// over two lanes (rm_small.h, LPR; 16,384 rays: 18.6 vs 19.7 us, 4,096: 15.9 vs 19.2; from
-// 65,536 rays the SIMDs are full and one lane per ray is faster, 25.6 vs 28.7). Env
-// RM_SMALL_LPR=1 / 2 forces one or two.
-int small_lpr(const Call& c, long long n) {
-  if (c.mode != kTrain || env_is("RM_SMALL_LPR", '1')) return 1;
-  return env_is("RM_SMALL_LPR", '2') || n <= 32768 ? 2 : 1;
-}
-
-int run_small(rm_context* ctx, const Call& c, KArgs& a, long long n) {
-  const bool has_bwd = c.mode == kBwd || c.mode == kTrain;
-  const int lpr = small_lpr(c, n), rpb = kBlock / lpr;
-  int rc;
-  if (has_bwd && (rc = ensure_ws(ctx, ws_need(n, a.M, rpb))) != RM_OK) return rc;
-  if (!ctx->arrivals) {
-    RM_HIP(ctx, hipMalloc(&ctx->arrivals, 64));
-    RM_HIP(ctx, hipMemsetAsync(ctx->arrivals, 0, 64, ctx->stream));
-  }
-  long long done = 0;
-  bool first = true;
-  while (done < n) {
-    const long long nb = std::min<long long>((n - done + rpb - 1) / rpb, max_blocks_per_launch());
-    const long long nr = std::min<long long>(n - done, nb * rpb);
-    a.ray_begin = done;
-    a.n_rays = nr;
-    a.partials = static_cast<float*>(ctx->ws);
-#ifdef RM_BLOCK_TRACE
-    if (!ctx->btrace)
-      RM_HIP(ctx, hipMalloc(&ctx->btrace, sizeof(unsigned long long) * kTraceWords * kWaves * (size_t)kMaxBlocksPerLaunch));
-    RM_HIP(ctx, hipMemsetAsync(ctx->btrace, 0, sizeof(unsigned long long) * kTraceWords * kWaves * (size_t)(nb + 1), ctx->stream));
-    a.btrace = ctx->btrace;
-    ctx->btrace_waves = (nb + (c.fused && c.fused->adam ? 1 : 0)) * kWaves;
-#endif
-    SmallArgs sa;
-    std::memset(&sa, 0, sizeof sa);
-    if (c.fused) sa = *c.fused;
-    if (has_bwd) sa.fin = final_args(c, first);
-    sa.arrivals = ctx->arrivals;
-    sa.final_in_kernel = has_bwd && nb <= kSmallFinalMaxBlocks ? 1 : 0;
-    if (c.fused && (!sa.final_in_kernel || nr != n))  // rm_train_iteration / _step_sampled checked this
-      return fail(ctx, RM_ERR_INVALID_ARG, "fused iteration needs one launch of <= %d blocks", kSmallFinalMaxBlocks);
-    const bool extra = c.fused && sa.adam;  // the launch's extra (optimizer) block
-    if (ctx->stats_dev) {
-      ctx->stats_blocks += nb;
-      ctx->stats_waves += nb * kWaves;
-    }
-    if (extra) {  // the extra block's optimizer part (rm_small.h)
-      if (!ctx->opt_pre) RM_HIP(ctx, hipMalloc(&ctx->opt_pre, sizeof(float) * (4 * kOptPreStride + 2)));
-      sa.opt_pre = ctx->opt_pre;
-      ctx->opt_prepared = false;  // a preparing call records its arguments after the launch
-    }
-    hipEvent_t ev0, ev1;
-    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
-    const dim3 grid((unsigned)(nb + (extra ? 1 : 0)));
-    if (c.fused && lpr == 2) launch_small_m<kTrain, true, 2>(a.M, grid, ctx->stream, a, sa, ev0, ev1);
-    else if (c.fused) launch_small_m<kTrain, true>(a.M, grid, ctx->stream, a, sa, ev0, ev1);
-    else if (c.mode == kFwd) launch_small_m<kFwd>(a.M, grid, ctx->stream, a, sa, ev0, ev1);
-    else if (c.mode == kBwd) launch_small_m<kBwd>(a.M, grid, ctx->stream, a, sa, ev0, ev1);
-    else if (lpr == 2) launch_small_m<kTrain, false, 2>(a.M, grid, ctx->stream, a, sa, ev0, ev1);
-    else launch_small_m<kTrain>(a.M, grid, ctx->stream, a, sa, ev0, ev1);
-    RM_HIP(ctx, hipGetLastError());
-    if (has_bwd && !sa.final_in_kernel && (rc = reduce_and_finalize(ctx, c, a, nb, first)) != RM_OK) return rc;
-    done += nr;
-    first = false;
-  }
-  return RM_OK;
-}
-
-template <int MODE>
-void launch_escape(bool cam, dim3 grid, hipStream_t st, const KArgs& a, int* flags) {
-  if (cam)
-    hipLaunchKernelGGL((rm_escape_kernel<MODE, true>), grid, dim3(kBlock), 0, st, a, flags);
-  else
-    hipLaunchKernelGGL((rm_escape_kernel<MODE, false>), grid, dim3(kBlock), 0, st, a, flags);
-}
-
-template <int MODE>
-void launch_cont(bool cam, dim3 grid, size_t lds, hipStream_t st, const KArgs& a, hipEvent_t ev0, hipEvent_t ev1) {
-  const dim3 blk(64 * kSplitWaves);
-  if (cam) hipExtLaunchKernelGGL((rm_cont_kernel<MODE, true>), grid, blk, (uint32_t)lds, st, ev0, ev1, 0u, a);
-  else hipExtLaunchKernelGGL((rm_cont_kernel<MODE, false>), grid, blk, (uint32_t)lds, st, ev0, ev1, 0u, a);
-}
-
-template <int MODE>
-void launch_ray(bool cam, bool split, dim3 grid, size_t lds, hipStream_t st, const KArgs& a, hipEvent_t ev0,
-                hipEvent_t ev1) {
-  // With timing on, the start/stop timestamps come from the kernel's own dispatch packet
-  // (hipExtLaunchKernel): no extra barrier packets or cache flushes around the launch.
-  const dim3 blk(split ? 64 * kSplitWaves : kBlock);
-  const uint32_t sh = (uint32_t)lds;
-  if (split) {
-    if (cam) hipExtLaunchKernelGGL((rm_ray_kernel<MODE, true, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
-    else hipExtLaunchKernelGGL((rm_ray_kernel<MODE, false, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
-  } else {
-    if (cam) hipExtLaunchKernelGGL((rm_ray_kernel<MODE, true, false>), grid, blk, sh, st, ev0, ev1, 0u, a);
-    else hipExtLaunchKernelGGL((rm_ray_kernel<MODE, false, false>), grid, blk, sh, st, ev0, ev1, 0u, a);
-  }
-}
-
-// Camera bases of a call with more than kInlineCams views: built on the host (make_basis), staged
-// in one of kCamRing pinned slots and copied to the context's device table on its stream (the
-// copy is ordered after the previous call's kernels, so one device table serves every call; a
-// pinned slot is rewritten only after its previous copy has run).
-constexpr int kCamRing = 32;  // calls of > 16 views in flight before the host waits for a slot
-static_assert(sizeof(rm_context::cam_ev) / sizeof(hipEvent_t) == kCamRing, "one event per staging slot");
-int upload_cams(rm_context* ctx, const Call& c, KArgs& a) {
-  int rc;
-  if (!ctx->cams_dev) {
-    if (hipMalloc(&ctx->cams_dev, sizeof(CamBasis) * RM_MAX_VIEWS_PER_CALL) != hipSuccess)
-      return fail(ctx, RM_ERR_OOM, "camera table");
-    if (hipHostMalloc(&ctx->cams_pin, sizeof(CamBasis) * RM_MAX_VIEWS_PER_CALL * kCamRing) != hipSuccess)
-      return fail(ctx, RM_ERR_OOM, "camera staging");
-    for (hipEvent_t& e : ctx->cam_ev) RM_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  RM_HIP(ctx, hipStreamIsCapturing(ctx->stream, &cap));
-  if (cap != hipStreamCaptureStatusNone) {
-    // under hipGraph capture nothing may wait or stage: the call must find its views in the device
-    // table already -- an eager call with the same views on this context uploaded them -- and the
-    // replays read that table (the caller keeps it: no call with other views on this context)
-    std::vector<CamBasis> want(c.views);
-    for (int v = 0; v < c.views; ++v)
-      if ((rc = make_basis(ctx, c.cams[v], c.W, c.H, want[v])) != RM_OK) return rc;
-    if (ctx->cams_shadow.size() != want.size() ||
-        std::memcmp(ctx->cams_shadow.data(), want.data(), sizeof(CamBasis) * want.size()) != 0)
-      return fail(ctx, RM_ERR_UNSUPPORTED,
-                  "a captured call of %d views reads the context's camera table: run the same call once before "
-                  "the capture", c.views);
-    a.cams_dev = ctx->cams_dev;
-    return RM_OK;
-  }
-  const int slot = ctx->cam_slot;
-  ctx->cam_slot = (slot + 1) % kCamRing;
-  RM_HIP(ctx, hipEventSynchronize(ctx->cam_ev[slot]));
-  CamBasis* pin = ctx->cams_pin + (size_t)slot * RM_MAX_VIEWS_PER_CALL;
-  for (int v = 0; v < c.views; ++v)
-    if ((rc = make_basis(ctx, c.cams[v], c.W, c.H, pin[v])) != RM_OK) return rc;
-  RM_HIP(ctx, hipMemcpyAsync(ctx->cams_dev, pin, sizeof(CamBasis) * c.views, hipMemcpyHostToDevice, ctx->stream));
-  RM_HIP(ctx, hipEventRecord(ctx->cam_ev[slot], ctx->stream));
-  ctx->cams_shadow.assign(pin, pin + c.views);
-  a.cams_dev = ctx->cams_dev;
-  return RM_OK;
-}
-
-int run(rm_context* ctx, const Call& c) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  // a prepared optimizer step is for the rm_optimizer_step right after its own sampled step: any
-  // other call in between may change the parameters it was prepared on (sampled_step sets it again)
-  ctx->opt_prepared = false;
-  int rc;
-  if ((rc = check_scene(ctx, c.scene, c.mode != kRender)) != RM_OK) return rc;
-  if ((rc = check_march(ctx, c.march)) != RM_OK) return rc;
-  KArgs a;
-  std::memset(&a, 0, sizeof a);
-  if (c.cam) {
-    if (!c.cams) return fail(ctx, RM_ERR_INVALID_ARG, "cams is NULL");
-    if (c.views < 1 || c.views > RM_MAX_VIEWS_PER_CALL)
-      return fail(ctx, RM_ERR_INVALID_ARG, "num_views %d out of [1, %d]", c.views, RM_MAX_VIEWS_PER_CALL);
-    if (c.W < 1 || c.H < 1 || (long long)c.W * c.H > (1LL << 28))
-      return fail(ctx, RM_ERR_INVALID_ARG, "bad image size %dx%d", c.W, c.H);
-    a.cams_dev = nullptr;
-    if (c.views <= kInlineCams) {
-      for (int v = 0; v < c.views; ++v)
-        if ((rc = make_basis(ctx, c.cams[v], c.W, c.H, a.cams[v])) != RM_OK) return rc;
-    } else if ((rc = upload_cams(ctx, c, a)) != RM_OK) {
-      return rc;
-    }
-    a.width = c.W;
-    a.height = c.H;
-    // Compact 16x16 tiles per block (8x8 per wave): more waves whose rays all miss the scene
-    // leave the march early (68 % vs 62 % of waves at the metric view, +3-4 %).
-    a.tiling = (c.W % 16 == 0 && c.H % 16 == 0) ? 2 : 0;
-    a.num_views = c.views;
-  } else {
-    if (c.n < 0) return fail(ctx, RM_ERR_INVALID_ARG, "num_rays %lld < 0", c.n);
-    if (c.n > 0 && (!c.org || !c.dir)) return fail(ctx, RM_ERR_INVALID_ARG, "ray_org/ray_dir is NULL");
-  }
-  const long long n = c.cam ? (long long)c.views * c.W * c.H : c.n;
-  if ((c.mode == kFwd || c.mode == kRender) && n > 0 && !c.out && !c.t_out && !c.dbg) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
-  if (c.mode == kBwd && n > 0 && !c.gout) return fail(ctx, RM_ERR_INVALID_ARG, "grad_out is NULL");
-  if (c.mode == kTrain && n > 0 && !c.targets) return fail(ctx, RM_ERR_INVALID_ARG, "targets is NULL");
-  const bool has_bwd = c.mode == kBwd || c.mode == kTrain;
-  if (has_bwd && !c.grads) return fail(ctx, RM_ERR_INVALID_ARG, "grads is NULL");
-
-  const int M = c.scene->num_spheres;
-  const int Mpad = pad_spheres(M);
-  a.org = c.org;
-  a.dir = c.dir;
-  a.centers = c.scene->centers;
-  if ((c.march->flags & RM_MARCH_COLOR_F16) != 0) {
-    a.colors = nullptr;
-    a.colors_h = reinterpret_cast<const _Float16*>(c.scene->colors);
-  } else {
-    a.colors = c.scene->colors;
-  }
-  a.radius = c.scene->radius;
-  a.light_dir = c.scene->light_dir;
-  a.ambient = c.scene->ambient;
-  a.M = M;
-  a.Mpad = Mpad;
-  a.steps = c.march->steps;
-  a.k = c.march->smooth_k;
-  a.eps = c.march->normal_eps;
-  a.csharp = c.march->color_sharpness;
-  a.msharp = c.march->mask_sharpness;
-  a.out = c.out;
-  a.t_out = c.t_out;
-  a.t_in = c.t_in;
-  a.gout = c.gout;
-  a.targets = c.targets;
-  a.progress = c.progress;
-  a.inv_count = c.inv_count;
-  a.sdev = ctx->sdev;
-  a.dbg = c.dbg;
-  // Escape skipping needs the mask to be exactly 0 at the certified distance: sigmoid(-msharp D)
-  // once msharp log2(e) D > 128 overflows exp2 (use 160), exp(-10 D^2) in kRender long before 50.
-  const bool mask_vanishes = c.mode == kRender || a.msharp > 0.0f;
-  // Split march (RM_MARCH_SPLIT): forced by the flag or env RM_SPLIT=1, automatic by sphere count
-  // and rays per launch (kSplitMinSpheres / kSplitMaxRays, kSplitMinSpheresWide / ...Wide); never with
-  // RM_MARCH_NO_SPLIT / env RM_SPLIT=0, in the renderer.rs mode or with the escape pre-pass.
-  bool split = false;
-  if (c.mode != kRender && (c.march->flags & RM_MARCH_SKIP_ESCAPED) == 0) {
-    const char* e = std::getenv("RM_SPLIT");
-    const long long n_all = c.cam ? (long long)c.views * c.W * c.H : c.n;
-    if ((c.march->flags & RM_MARCH_SPLIT) != 0 || (e && e[0] == '1')) split = true;
-    else if ((c.march->flags & RM_MARCH_NO_SPLIT) == 0 && !(e && e[0] == '0'))
-      split = (M >= kSplitMinSpheres && n_all <= kSplitMaxRays) || (M >= kSplitMinSpheresWide && n_all <= kSplitMaxRaysWide);
-  }
-  a.split = split ? 1 : 0;
-  // every split launch runs in ray mode (the scene-uniform shift, per-ray retirement and the
-  // ray-level continuation: the split kernels are compiled for it, see KArgs::cont_cap)
-  const int rpb = split ? kSplitRays : kBlock;  // rays per block
-  a.cull = ((c.march->flags & RM_MARCH_SKIP_ESCAPED) != 0 && mask_vanishes && !c.t_out && !c.dbg && !split) ? 1 : 0;
-  a.cull_min_d = c.mode == kRender ? 50.0f : std::max(50.0f, 160.0f / (a.msharp * 1.44269504f));
-  a.lse_slack = (float)(std::log((double)M) / (double)a.k * (1.0 + 1e-6)) + 1e-7f;
-  // Escaped-ray early exit: the mask must be exactly 0 at distance gone_d -- exp2 of
-  // msharp log2(e) D overflows at 128 (use 130; the reference's sigmoid(-15 D) is 0 from 5.92);
-  // exp(-10 D^2) underflows long before 6.
-  // Gone rays (the march) in every mode but the diagnostics; the exit itself not when the march t
-  // of every ray is requested (t_out) or with RM_MARCH_NO_EARLY_EXIT.
-  a.gone_d = 0.0f;
-  if (!c.dbg) {
-    if (c.mode == kRender) a.gone_d = 6.0f;
-    else if (a.msharp > 0.0f) a.gone_d = std::max(6.0f, 130.0f / (a.msharp * 1.44269504f));
-  }
-  a.early_exit = a.gone_d > 0.0f && (c.march->flags & RM_MARCH_NO_EARLY_EXIT) == 0 && !c.t_out ? 1 : 0;
-  if ((c.march->flags & RM_MARCH_ROW_ORDER) != 0) a.tiling = 0;
-  a.mfma = (c.march->flags & RM_MARCH_VALU_ONLY) == 0;
-  a.shift_max = (c.march->flags & RM_MARCH_FORCE_MAX_SHIFT) != 0;
-  if (c.mode == kRender) {  // renderer.rs:27-32, normalised in f32 on the host like the reference
-    const float lv[3] = {-0.5f, 0.5f, -1.0f};
-    const float len = std::sqrt(lv[0] * lv[0] + lv[1] * lv[1] + lv[2] * lv[2]);
-    for (int i = 0; i < 3; ++i) a.light_fixed[i] = lv[i] / len;
-  }
-  a.rec = rec_floats(Mpad);
-  if (use_small(c, M, n)) return run_small(ctx, c, a, n);
-  if (c.fused) return fail(ctx, RM_ERR_INVALID_ARG, "fused iteration outside the small kernel");
-  // sphere records of this call (rm_prep_kernel): read by every sweep through scalar loads
-  if (n > 0) {
-    const int np = Mpad / 2, nprep = (np + 255) / 256;
-    const size_t need = rec_bytes(np, nprep);
-    if (need > ctx->rec_bytes) {
-      if (ctx->rec) {
-        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        RM_HIP(ctx, hipFree(ctx->rec));
-        ctx->rec = nullptr;
-        ctx->rec_bytes = 0;
-      }
-      if (hipMalloc(&ctx->rec, need) != hipSuccess) return fail(ctx, RM_ERR_OOM, "record buffer (%zu B)", need);
-      ctx->rec_bytes = need;
-    }
-    // camera mode: the per-view first march step at the eye, shared by every ray of the view
-    a.origin = (c.cam && (c.march->flags & (RM_MARCH_PER_RAY_ORIGIN | RM_MARCH_FORCE_MAX_SHIFT)) == 0)
-                   ? reinterpret_cast<float*>((char*)ctx->rec + origin_offset(np, nprep))
-                   : nullptr;
-    hipLaunchKernelGGL(rm_prep_kernel, dim3(nprep), dim3(256), 0, ctx->stream, a, (float4*)ctx->rec);
-    RM_HIP(ctx, hipGetLastError());
-    if (nprep > 1) {
-      float* hdr = reinterpret_cast<float*>((char*)ctx->rec + (size_t)np * (7 * 16 + 8));
-      float* esc = reinterpret_cast<float*>((char*)ctx->rec + esc_offset(np, nprep));
-      hipLaunchKernelGGL(rm_prep_finish, dim3(1), dim3(256), 0, ctx->stream, a, hdr, esc, nprep);
-      RM_HIP(ctx, hipGetLastError());
-    }
-    if (a.origin != nullptr) {
-      if (a.split)
-        hipLaunchKernelGGL(rm_origin_kernel<true>, dim3(c.views), dim3(64 * kSplitWaves), 0, ctx->stream, a,
-                           (const float4*)ctx->rec, nprep);
-      else
-        hipLaunchKernelGGL(rm_origin_kernel<false>, dim3(c.views), dim3(64), 0, ctx->stream, a, (const float4*)ctx->rec,
-                           nprep);
-      RM_HIP(ctx, hipGetLastError());
-    }
-    a.rec_buf = (const float4*)ctx->rec;
-  }
-  const size_t lds = lds_bytes();
-
-  if (has_bwd) {
-    if ((rc = ensure_ws(ctx, ws_need(std::max<long long>(n, 1), M, rpb))) != RM_OK) return rc;
-  }
-  float* P = static_cast<float*>(ctx->ws);
-
-  if (n == 0) {  // nothing to render; backward/train still define their outputs
-    if (!has_bwd) return RM_OK;
-  }
-  long long done = 0;
-  bool first = true;
-  do {
-    const long long blocks_left = (n - done + rpb - 1) / rpb;
-    const long long nb = std::min<long long>(blocks_left, max_blocks_per_launch());
-    const long long nr = std::min<long long>(n - done, nb * rpb);
-    a.ray_begin = done;
-    a.n_rays = nr;
-    a.partials = P;
-    a.stats = ctx->stats_dev;
-    if (ctx->stats_dev) {
-      ctx->stats_blocks += nb;
-      ctx->stats_waves += nb * (split ? 1 : kWaves);
-    }
-    a.esc_flags = nullptr;
-    a.block_order = nullptr;
-    a.olist_r = nullptr;
-    a.ocnt_r = nullptr;
-    a.olist_w = nullptr;
-    a.ocnt_w = nullptr;
-    a.ocnt_z = nullptr;
-    a.oturn = nullptr;
-    const long long npix = (long long)c.W * c.H;
-    if (c.cam && a.tiling == 2 && nb > 1 && done % npix == 0 && nr % npix == 0 && nr == nb * rpb &&
-        (c.march->flags & RM_MARCH_NATURAL_ORDER) == 0) {
-      if ((rc = ensure_block_order(ctx, c.W / 16, c.H / 16, 256 / rpb)) != RM_OK) return rc;
-      a.block_order = ctx->block_order;
-      a.order_views = (int)(nr / npix);
-      a.order_tiles = (int)(npix / rpb);
-    }
-    // cost-ordered dispatch from the previous launch over the same views (single-launch calls)
-    const bool has_rec = c.mode == kBwd || c.mode == kTrain;
-    unsigned long long key = 0;
-    if (a.block_order != nullptr && has_rec && nb == blocks_left && done == 0 &&
-        (c.march->flags & RM_MARCH_STATIC_ORDER) == 0) {
-      key = ((unsigned long long)c.W << 48) ^ ((unsigned long long)c.H << 32) ^ ((unsigned long long)c.views << 24) ^
-            ((unsigned long long)Mpad << 1) ^ 1ull ^ ((unsigned long long)split << 2);
-      constexpr int kCls = RM_ORDER_CLASSES;
-      if (!ctx->olist) {
-        RM_HIP(ctx, hipMalloc(&ctx->olist, sizeof(int) * 3 * kCls * kMaxBlocksPerLaunch));
-        // the three sets' counts, then the turn word, RM_ORDER_CNT_STRIDE ints apart
-        RM_HIP(ctx, hipMalloc(&ctx->ocnt, sizeof(int) * 4 * RM_ORDER_CNT_STRIDE));
-        RM_HIP(ctx, hipMemsetAsync(ctx->ocnt, 0, sizeof(int) * 4 * RM_ORDER_CNT_STRIDE, ctx->stream));
-        ctx->oturn = ctx->ocnt + 3 * RM_ORDER_CNT_STRIDE;
-      }
-      // three list sets in rotation: the previous launch's (read), this launch's (appended;
-      // cleared by the previous launch) and the next launch's (cleared by this one); which is which
-      // the kernel reads from the device turn word, advanced by this call's reduction (order_sets)
-      if (ctx->cost_valid && ctx->cost_key == key) {
-        a.olist_r = ctx->olist;
-        a.ocnt_r = ctx->ocnt;
-      }
-      a.olist_w = ctx->olist;
-      a.ocnt_w = ctx->ocnt;
-      a.ocnt_z = ctx->ocnt;
-      a.oturn = ctx->oturn;
-      if (const char* e = std::getenv("RM_DEBUG_SKIP_ORDER_CLEAR"))  // recovery test (rm_debug_order_counts)
-        if (e[0] == '1') a.ocnt_z = nullptr;
-    }
-    if (has_rec) {
-      ctx->cost_valid = key != 0;
-      ctx->cost_key = key;
-    }
-    if (nb > 0 && a.cull) {
-      if (!ctx->esc_flags) RM_HIP(ctx, hipMalloc(&ctx->esc_flags, sizeof(int) * kMaxBlocksPerLaunch));
-      const dim3 g((unsigned)nb);
-      if (c.mode == kFwd) launch_escape<kFwd>(c.cam, g, ctx->stream, a, ctx->esc_flags);
-      else if (c.mode == kBwd) launch_escape<kBwd>(c.cam, g, ctx->stream, a, ctx->esc_flags);
-      else if (c.mode == kTrain) launch_escape<kTrain>(c.cam, g, ctx->stream, a, ctx->esc_flags);
-      else launch_escape<kRender>(c.cam, g, ctx->stream, a, ctx->esc_flags);
-      RM_HIP(ctx, hipGetLastError());
-      a.esc_flags = ctx->esc_flags;
-    }
-    if (nb > 0) {
-      hipEvent_t ev0, ev1;
-      if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
-      dim3 grid((unsigned)nb);
-#ifdef RM_BLOCK_TRACE
-      if (!ctx->btrace)
-        RM_HIP(ctx, hipMalloc(&ctx->btrace, sizeof(unsigned long long) * kTraceWords * kWaves * (size_t)kMaxBlocksPerLaunch));
-      a.btrace = ctx->btrace;
-      ctx->btrace_waves = nb * kWaves;
-#endif
-      // Split continuation (bwd / train launches with the early exit; KArgs::cont_cap): the groups
-      // whose rays still march at step caps[0] stop there and list themselves and those rays;
-      // continuation launches at increasing steps (split_cont_caps) march the listed rays packed
-      // into full blocks -- spread evenly over the CUs, where the first launch placed the groups by
-      // a cost order that only partly predicts which of them march every step -- and a resume
-      // launch finishes the listed groups. Bit-identical to one launch (tests/test_gpu_split.py).
-      int caps[kMaxCont + 1];
-      const int ncaps = split_cont_caps(a.steps, caps);
-      const bool cont = split && c.mode != kRender && c.mode != kFwd && a.early_exit && ncaps > 0 &&
-                        a.steps >= 2 * caps[0];
-      int* glist = nullptr;   // the deferred groups and their count
-      int* gcount = nullptr;
-      int* rlists[2] = {nullptr, nullptr};
-      int* rcounts[2] = {nullptr, nullptr};
-      if (cont) {
-        const long long rays = nb * kSplitRays;
-        // per ray 8 state rows, per group 2 words (KArgs::cont_state); the group list and its count;
-        // two ray lists of up to `rays` entries and their counts
-        const size_t need = (size_t)(8 * rays + 2 * nb) * sizeof(float) + (size_t)(nb + 8 + 16) * sizeof(int) +
-                            (size_t)(2 * rays + 16) * sizeof(int);
-        if (ctx->cont_bytes < need) {
-          if (ctx->cont_buf) RM_HIP(ctx, hipFree(ctx->cont_buf));
-          ctx->cont_buf = nullptr;
-          ctx->cont_bytes = 0;
-          RM_HIP(ctx, hipMalloc(&ctx->cont_buf, need));
-          ctx->cont_bytes = need;
-        }
-        glist = reinterpret_cast<int*>(ctx->cont_buf + 8 * rays + 2 * nb);
-        gcount = glist + nb;
-        rcounts[0] = gcount + 8;  // the three counts 32 bytes apart
-        rcounts[1] = rcounts[0] + 8;
-        rlists[0] = rcounts[1] + 8;
-        rlists[1] = rlists[0] + rays;
-        a.cont_state = ctx->cont_buf;
-        a.cont_rays = rays;
-        a.cont_list_w = glist;
-        a.cont_count_w = gcount;
-        a.cont_cap = caps[0];
-        a.cont_resume = 0;
-        a.ray_list_w = rlists[0];  // the first launch appends the marching rays to ray list 0
-        a.ray_count_w = rcounts[0];
-        RM_HIP(ctx, hipMemsetAsync(gcount, 0, (8 + 16) * sizeof(int), ctx->stream));  // the three counts
-      }
-      if (c.mode == kFwd) launch_ray<kFwd>(c.cam, split, grid, lds, ctx->stream, a, ev0, ev1);
-      else if (c.mode == kBwd) launch_ray<kBwd>(c.cam, split, grid, lds, ctx->stream, a, ev0, ev1);
-      else if (c.mode == kTrain) launch_ray<kTrain>(c.cam, split, grid, lds, ctx->stream, a, ev0, ev1);
-      else launch_ray<kRender>(c.cam, false, grid, lds, ctx->stream, a, ev0, ev1);
-      RM_HIP(ctx, hipGetLastError());
-      // continuation k marches the rays of ray list k % 2 (deferring at the next cap into
-      // list (k + 1) % 2, whose count is cleared first: continuation k - 1 read it), then one resume
-      // launch runs the deferred groups' post-march forward and backward from their final states
-      for (int ph = 0; cont && ph < ncaps; ++ph) {
-        KArgs b = a;
-        b.ray_cont = 1;
-        b.cont_resume = caps[ph];
-        b.cont_cap = caps[ph + 1];
-        b.ray_list = rlists[ph & 1];
-        b.ray_count = rcounts[ph & 1];
-        b.ray_list_w = rlists[(ph + 1) & 1];
-        b.ray_count_w = rcounts[(ph + 1) & 1];
-        if (b.cont_cap > 0) RM_HIP(ctx, hipMemsetAsync(b.ray_count_w, 0, sizeof(int), ctx->stream));
-        b.cont_list_w = nullptr;
-        b.cont_count_w = nullptr;
-        b.ocnt_z = nullptr;
-        b.olist_r = nullptr;
-        b.ocnt_r = nullptr;
-        b.ocnt_w = nullptr;  // no groups of its own: the resume launch appends them
-        b.olist_w = nullptr;
-        hipEvent_t e0, e1;
-        if ((rc = next_events(ctx, e0, e1)) != RM_OK) return rc;
-        if (c.mode == kBwd) launch_cont<kBwd>(c.cam, grid, lds, ctx->stream, b, e0, e1);
-        else launch_cont<kTrain>(c.cam, grid, lds, ctx->stream, b, e0, e1);
-        RM_HIP(ctx, hipGetLastError());
-      }
-      if (cont) {
-        KArgs b = a;
-        b.cont_resume = a.steps;
-        b.cont_cap = 0;
-        b.cont_list = glist;
-        b.cont_count = gcount;
-        b.cont_list_w = nullptr;
-        b.cont_count_w = nullptr;
-        b.ray_list_w = nullptr;
-        b.ray_count_w = nullptr;
-        b.ocnt_z = nullptr;
-        b.olist_r = nullptr;
-        b.ocnt_r = nullptr;
-        hipEvent_t e0, e1;
-        if ((rc = next_events(ctx, e0, e1)) != RM_OK) return rc;
-        if (c.mode == kBwd) launch_cont<kBwd>(c.cam, grid, lds, ctx->stream, b, e0, e1);
-        else launch_cont<kTrain>(c.cam, grid, lds, ctx->stream, b, e0, e1);
-        RM_HIP(ctx, hipGetLastError());
-      }
-    }
-    if (has_bwd && (rc = reduce_and_finalize(ctx, c, a, nb, first, first && nb == blocks_left)) != RM_OK) return rc;
-    done += nr;
-    first = false;
-  } while (done < n);
-  return RM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-#ifndef RM_SOURCE_SHA
-#define RM_SOURCE_SHA "unknown"  // _build.py passes the sha256 of the kernel sources
-#endif
-const char* rm_version(void) { return "burn_raymarching_amd 0.1.0 (gfx950) src " RM_SOURCE_SHA; }
-
-int rm_create(int32_t device, void* stream, rm_context** out_ctx) {
-  if (!out_ctx) return RM_ERR_INVALID_ARG;
-  *out_ctx = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return RM_ERR_HIP;
-  if (hipSetDevice(device) != hipSuccess) return RM_ERR_HIP;
-  rm_context* ctx = new rm_context();
-  ctx->device = device;
-  ctx->stream = static_cast<hipStream_t>(stream);
-  *out_ctx = ctx;
-  return RM_OK;
-}
-
-int rm_bind_step_scalars(rm_context* ctx, rm_step_scalars* dev) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->sdev = dev;
-  return RM_OK;
-}
-
-int rm_set_stream(rm_context* ctx, void* stream) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->stream = static_cast<hipStream_t>(stream);
-  return RM_OK;
-}
-
-int rm_timing_enable(rm_context* ctx, int32_t enable) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->timing = enable != 0;
-  // pre-create a pool so event creation stays out of timed regions
-  while (ctx->timing && ctx->events.size() < 256) {
-    std::pair<hipEvent_t, hipEvent_t> pr;
-    RM_HIP(ctx, hipEventCreate(&pr.first));
-    RM_HIP(ctx, hipEventCreate(&pr.second));
-    ctx->events.push_back(pr);
-  }
-  return RM_OK;
-}
-
-int rm_timing_collect(rm_context* ctx, double* total_ms, int64_t* launches, int32_t reset) {
-  if (!ctx || !total_ms || !launches) return RM_ERR_INVALID_ARG;
-  double acc = 0.0;
-  for (size_t i = 0; i < ctx->events_used; ++i) {
-    RM_HIP(ctx, hipEventSynchronize(ctx->events[i].second));
-    float ms = 0.0f;
-    RM_HIP(ctx, hipEventElapsedTime(&ms, ctx->events[i].first, ctx->events[i].second));
-    acc += ms;
-  }
-  *total_ms = acc;
-  *launches = (int64_t)ctx->events_used;
-  if (reset) ctx->events_used = 0;
-  return RM_OK;
-}
-
-int rm_debug_order_counts(rm_context* ctx, int32_t* counts, int32_t capacity, int32_t* classes, int32_t* next_set) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  constexpr int kCls = RM_ORDER_CLASSES;
-  if (classes) *classes = kCls;
-  if (counts && capacity < 3 * kCls) return fail(ctx, RM_ERR_INVALID_ARG, "counts needs %d entries", 3 * kCls);
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<int> host(4 * RM_ORDER_CNT_STRIDE, 0);  // the sets' counts and the device turn word
-  if (ctx->ocnt) RM_HIP(ctx, hipMemcpy(host.data(), ctx->ocnt, sizeof(int) * host.size(), hipMemcpyDeviceToHost));
-  if (next_set) *next_set = host[3 * RM_ORDER_CNT_STRIDE];
-  if (counts)
-    for (int st = 0; st < 3; ++st)
-      for (int c = 0; c < kCls; ++c) counts[st * kCls + c] = host[st * RM_ORDER_CNT_STRIDE + c * RM_ORDER_CLS_STRIDE];
-  return RM_OK;
-}
-
-#ifdef RM_BLOCK_TRACE
-// Measurement build only (not in include/raymarch.h): the per-wave records of the last per-ray
-// launch, 4 x u64 per wave in launch order (see rm_ray_kernel). Synchronises the stream.
-int rm_debug_block_trace(rm_context* ctx, unsigned long long* host, int64_t cap_waves, int64_t* n_waves) {
-  if (!ctx || !host || !n_waves) return RM_ERR_INVALID_ARG;
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const long long n = std::min<long long>(ctx->btrace_waves, cap_waves);
-  *n_waves = n;
-  if (n > 0) RM_HIP(ctx, hipMemcpy(host, ctx->btrace, sizeof(unsigned long long) * kTraceWords * n, hipMemcpyDeviceToHost));
-  return RM_OK;
-}
-#endif
-
-int rm_debug_stall(rm_context* ctx, int32_t max_ms) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  if (max_ms < 1 || max_ms > 600000) return fail(ctx, RM_ERR_INVALID_ARG, "max_ms %d out of [1, 600000]", max_ms);
-  if (!ctx->stall_flag)
-    RM_HIP(ctx, hipHostMalloc(reinterpret_cast<void**>(&ctx->stall_flag), 64, hipHostMallocMapped | hipHostMallocCoherent));
-  __atomic_store_n(ctx->stall_flag, 0, __ATOMIC_RELEASE);
-  int* dflag = nullptr;
-  RM_HIP(ctx, hipHostGetDevicePointer(reinterpret_cast<void**>(&dflag), ctx->stall_flag, 0));
-  hipLaunchKernelGGL(rm::rm_stall_kernel, dim3(1), dim3(64), 0, ctx->stream, dflag,
-                     (unsigned long long)max_ms * 100000ull);  // s_memrealtime: 100 MHz
-  RM_HIP(ctx, hipGetLastError());
-  return RM_OK;
-}
-
-int rm_debug_stall_release(rm_context* ctx) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  if (ctx->stall_flag) __atomic_store_n(ctx->stall_flag, 1, __ATOMIC_RELEASE);
-  return RM_OK;
-}
-
-int rm_stats_enable(rm_context* ctx, int32_t enable) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  if (enable && !ctx->stats_dev) {
-    RM_HIP(ctx, hipMalloc(&ctx->stats_dev, kStatsWords * sizeof(unsigned long long)));
-    RM_HIP(ctx, hipMemsetAsync(ctx->stats_dev, 0, kStatsWords * sizeof(unsigned long long), ctx->stream));
-    ctx->stats_blocks = 0;
-    ctx->stats_waves = 0;
-  } else if (!enable && ctx->stats_dev) {
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    RM_HIP(ctx, hipFree(ctx->stats_dev));
-    ctx->stats_dev = nullptr;
-  }
-  return RM_OK;
-}
-
-int rm_stats_collect(rm_context* ctx, rm_stats* out, int32_t reset) {
-  if (!ctx || !out) return RM_ERR_INVALID_ARG;
-  if (!ctx->stats_dev) return fail(ctx, RM_ERR_INVALID_ARG, "stats are not enabled");
-  unsigned long long v[kStatsWords];
-  RM_HIP(ctx, hipMemcpyAsync(v, ctx->stats_dev, sizeof v, hipMemcpyDeviceToHost, ctx->stream));
-  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  out->blocks = ctx->stats_blocks;
-  out->blocks_skipped = (int64_t)v[0];
-  out->waves = ctx->stats_waves;
-  out->waves_exited = (int64_t)v[1];
-  out->steps_saved = (int64_t)v[2];
-  out->seeded_rays = (int64_t)v[4];
-  out->seeded_rays_a = (int64_t)v[5];
-  if (reset) {
-    RM_HIP(ctx, hipMemsetAsync(ctx->stats_dev, 0, sizeof v, ctx->stream));
-    ctx->stats_blocks = 0;
-    ctx->stats_waves = 0;
-  }
-  return RM_OK;
-}
-
-void rm_destroy(rm_context* ctx) {
-  if (!ctx) return;
-  if (ctx->stall_flag) {  // a pending stall ends before its flag goes away
-    __atomic_store_n(ctx->stall_flag, 1, __ATOMIC_RELEASE);
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipHostFree(ctx->stall_flag);
-  }
-  if (ctx->stats_dev || ctx->esc_flags || ctx->rec || ctx->block_order || ctx->olist || ctx->cont_buf) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->stats_dev) (void)hipFree(ctx->stats_dev);
-    if (ctx->esc_flags) (void)hipFree(ctx->esc_flags);
-    if (ctx->block_order) (void)hipFree(ctx->block_order);
-    if (ctx->olist) (void)hipFree(ctx->olist);
-    if (ctx->cont_buf) (void)hipFree(ctx->cont_buf);
-    if (ctx->ocnt) (void)hipFree(ctx->ocnt);
-    if (ctx->rec) (void)hipFree(ctx->rec);
-  }
-  if (ctx->arrivals || ctx->red_arrivals || ctx->batch || ctx->cams_dev || ctx->opt_pre || ctx->opt_arrival) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->arrivals) (void)hipFree(ctx->arrivals);
-    if (ctx->red_arrivals) (void)hipFree(ctx->red_arrivals);
-    if (ctx->batch) (void)hipFree(ctx->batch);
-    if (ctx->opt_pre) (void)hipFree(ctx->opt_pre);
-    if (ctx->opt_arrival) (void)hipFree(ctx->opt_arrival);
-    if (ctx->cams_dev) (void)hipFree(ctx->cams_dev);
-    if (ctx->cams_pin) (void)hipHostFree(ctx->cams_pin);
-    for (hipEvent_t& e : ctx->cam_ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  for (auto& pr : ctx->events) {
-    (void)hipEventDestroy(pr.first);
-    (void)hipEventDestroy(pr.second);
-  }
-  if (ctx->ws) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(ctx->ws);
-  }
-  if (ctx->rg_ws) {
-    (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(ctx->rg_ws);
-  }
-  delete ctx;
-}
-
-const char* rm_last_error(const rm_context* ctx) { return ctx ? ctx->err.c_str() : "NULL context"; }
-
-void rm_march_default(rm_march* m) {
-  if (!m) return;
-  m->steps = 40;             // renderer_diff.rs:22
-  m->smooth_k = 32.0f;       // train.rs:131 MAX_SMOOTH / preview train.rs:355
-  m->normal_eps = 1e-4f;     // scene.rs:91
-  m->color_sharpness = 10.0f; // renderer_diff.rs:74
-  m->mask_sharpness = 15.0f;  // renderer_diff.rs:88
-  m->flags = 0;
-}
-
-int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  if (max_rays < 0 || max_spheres < 1 || max_spheres > RM_MAX_SPHERES)
-    return fail(ctx, RM_ERR_INVALID_ARG, "bad reserve sizes");
-  // the small buffers the calls otherwise allocate on first use: the arrival counters of the
-  // in-kernel reductions (zeroed) and the fused iteration's optimizer hand-off
-  if (!ctx->arrivals) {
-    RM_HIP(ctx, hipMalloc(&ctx->arrivals, 64));
-    RM_HIP(ctx, hipMemsetAsync(ctx->arrivals, 0, 64, ctx->stream));
-  }
-  if (!ctx->red_arrivals) {
-    RM_HIP(ctx, hipMalloc(&ctx->red_arrivals, sizeof(unsigned) * kRedArrivals));
-    RM_HIP(ctx, hipMemsetAsync(ctx->red_arrivals, 0, sizeof(unsigned) * kRedArrivals, ctx->stream));
-  }
-  if (!ctx->opt_arrival) {
-    RM_HIP(ctx, hipMalloc(&ctx->opt_arrival, 128));
-    RM_HIP(ctx, hipMemsetAsync(ctx->opt_arrival, 0, 128, ctx->stream));
-  }
-  if (!ctx->opt_pre) RM_HIP(ctx, hipMalloc(&ctx->opt_pre, sizeof(float) * (4 * kOptPreStride + 2)));
-  int rc;
-  if ((rc = ensure_rg(ctx, rg_need(std::max<int64_t>(max_rays, 1)))) != RM_OK) return rc;
-  return ensure_ws(ctx, ws_need(std::max<int64_t>(max_rays, 1), max_spheres));
-}
-
-int rm_render_diff(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
-                   const rm_scene* scene, const rm_march* march, float* out, float* t_march) {
-  Call c;
-  c.mode = kFwd;
-  c.cam = false;
-  c.org = ray_org;
-  c.dir = ray_dir;
-  c.n = num_rays;
-  c.scene = scene;
-  c.march = march;
-  c.out = out;
-  c.t_out = t_march;
-  return run(ctx, c);
-}
-
-int rm_render_diff_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width, int32_t height,
-                          const rm_scene* scene, const rm_march* march, float* out, float* t_march) {
-  Call c;
-  c.mode = kFwd;
-  c.cam = true;
-  c.cams = cams;
-  c.views = num_views;
-  c.W = width;
-  c.H = height;
-  c.scene = scene;
-  c.march = march;
-  c.out = out;
-  c.t_out = t_march;
-  return run(ctx, c);
-}
-
-int rm_render_diff_backward(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
-                            const rm_scene* scene, const rm_march* march, const float* grad_out,
-                            const float* t_march, const rm_grads* grads, int32_t accumulate) {
-  Call c;
-  c.mode = kBwd;
-  c.cam = false;
-  c.org = ray_org;
-  c.dir = ray_dir;
-  c.n = num_rays;
-  c.scene = scene;
-  c.march = march;
-  c.gout = grad_out;
-  c.t_in = t_march;
-  c.grads = grads;
-  c.accumulate = accumulate;
-  return run(ctx, c);
-}
-
-int rm_render_diff_backward_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width,
-                                   int32_t height, const rm_scene* scene, const rm_march* march,
-                                   const float* grad_out, const float* t_march, const rm_grads* grads,
-                                   int32_t accumulate) {
-  Call c;
-  c.mode = kBwd;
-  c.cam = true;
-  c.cams = cams;
-  c.views = num_views;
-  c.W = width;
-  c.H = height;
-  c.scene = scene;
-  c.march = march;
-  c.gout = grad_out;
-  c.t_in = t_march;
-  c.grads = grads;
-  c.accumulate = accumulate;
-  return run(ctx, c);
-}
-
-int rm_train_step(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets,
-                  int64_t num_rays, float progress, float inv_count, const rm_scene* scene, const rm_march* march,
-                  const rm_grads* grads, float* loss_sum, float* out, int32_t accumulate) {
-  Call c;
-  c.mode = kTrain;
-  c.cam = false;
-  c.org = ray_org;
-  c.dir = ray_dir;
-  c.n = num_rays;
-  c.targets = targets;
-  c.progress = progress;
-  c.inv_count = inv_count;
-  c.scene = scene;
-  c.march = march;
-  c.grads = grads;
-  c.loss_sum = loss_sum;
-  c.out = out;
-  c.accumulate = accumulate;
-  return run(ctx, c);
-}
-
-int rm_train_step_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width, int32_t height,
-                         const float* targets, float progress, float inv_count, const rm_scene* scene,
-                         const rm_march* march, const rm_grads* grads, float* loss_sum, float* out,
-                         int32_t accumulate) {
-  Call c;
-  c.mode = kTrain;
-  c.cam = true;
-  c.cams = cams;
-  c.views = num_views;
-  c.W = width;
-  c.H = height;
-  c.targets = targets;
-  c.progress = progress;
-  c.inv_count = inv_count;
-  c.scene = scene;
-  c.march = march;
-  c.grads = grads;
-  c.loss_sum = loss_sum;
-  c.out = out;
-  c.accumulate = accumulate;
-  return run(ctx, c);
-}
-
-int rm_render(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays, const float* centers,
-              const float* colors, const float* radius, int32_t num_spheres, float* out) {
-  rm_scene sc{centers, colors, radius, nullptr, nullptr, num_spheres};
-  rm_march m;
-  rm_march_default(&m);  // 40 steps, k = 32, eps 1e-4, exp(-10 d) (renderer.rs:17-19, :52)
-  Call c;
-  c.mode = kRender;
-  c.cam = false;
-  c.org = ray_org;
-  c.dir = ray_dir;
-  c.n = num_rays;
-  c.scene = &sc;
-  c.march = &m;
-  c.out = out;
-  return run(ctx, c);
-}
-
-int rm_render_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width, int32_t height,
-                     const float* centers, const float* colors, const float* radius, int32_t num_spheres,
-                     float* out) {
-  rm_scene sc{centers, colors, radius, nullptr, nullptr, num_spheres};
-  rm_march m;
-  rm_march_default(&m);
-  Call c;
-  c.mode = kRender;
-  c.cam = true;
-  c.cams = cams;
-  c.views = num_views;
-  c.W = width;
-  c.H = height;
-  c.scene = &sc;
-  c.march = &m;
-  c.out = out;
-  return run(ctx, c);
-}
-
-int rm_debug_intermediates(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
-                           const rm_scene* scene, const rm_march* march, float* dbg) {
-  if (!dbg) return fail(ctx, RM_ERR_INVALID_ARG, "dbg is NULL");
-  Call c;
-  c.mode = kFwd;
-  c.cam = false;
-  c.org = ray_org;
-  c.dir = ray_dir;
-  c.n = num_rays;
-  c.scene = scene;
-  c.march = march;
-  c.dbg = dbg;
-  return run(ctx, c);
-}
-
-int rm_scene_activate(rm_context* ctx, const float* raw_packed, int32_t num_spheres, float* act_packed) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->opt_prepared = false;  // the parameters may have changed since a prepared step (see run)
-  if (!raw_packed || !act_packed) return fail(ctx, RM_ERR_INVALID_ARG, "NULL packed buffer");
-  if (num_spheres < 1 || num_spheres > RM_MAX_SPHERES) return fail(ctx, RM_ERR_INVALID_ARG, "bad num_spheres");
-  const int n = 7 * num_spheres + 4;
-  hipLaunchKernelGGL(rm::rm_activate_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, raw_packed,
-                     num_spheres, act_packed);
-  RM_HIP(ctx, hipGetLastError());
-  return RM_OK;
-}
-
-int rm_gather_rays(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets,
-                   int64_t num_src, const int32_t* indices, int64_t num_rays, float* out_org, float* out_dir,
-                   float* out_targets) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->opt_prepared = false;
-  if (num_rays < 0 || num_src < 0) return fail(ctx, RM_ERR_INVALID_ARG, "negative size");
-  if (num_rays == 0) return RM_OK;
-  if (!indices) return fail(ctx, RM_ERR_INVALID_ARG, "indices is NULL");
-  if ((out_org && !ray_org) || (out_dir && !ray_dir) || (out_targets && !targets))
-    return fail(ctx, RM_ERR_INVALID_ARG, "an output is requested without its source array");
-  if (!out_org && !out_dir && !out_targets) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
-  const long long nel = 3 * (long long)num_rays;
-  hipLaunchKernelGGL(rm::rm_gather_kernel, dim3((unsigned)((nel + 255) / 256)), dim3(256), 0, ctx->stream, ray_org,
-                     ray_dir, targets, (long long)num_src, indices, (long long)num_rays, out_org, out_dir,
-                     out_targets);
-  RM_HIP(ctx, hipGetLastError());
-  return RM_OK;
-}
-
-}  // extern "C"
-
-namespace {
-// the sampler's per-call key: (seed, stream, counter) mixed on the host
-unsigned long long sample_key(uint64_t seed, uint64_t stream, uint64_t counter) {
-  auto mix = [](unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-  };
-  return mix(mix(mix(seed) ^ stream) ^ counter);
-}
-}  // namespace
-
-extern "C" {
-
-int rm_sample_batch(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets, int64_t num_src,
-                    const int32_t* fg_indices, int64_t num_fg, int64_t n_uniform, int64_t n_fg, uint64_t seed,
-                    uint64_t stream, uint64_t counter, float* out_org, float* out_dir, float* out_targets,
-                    int32_t* indices_out) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->opt_prepared = false;
-  if (num_src < 0 || num_fg < 0 || n_uniform < 0 || n_fg < 0) return fail(ctx, RM_ERR_INVALID_ARG, "negative size");
-  const long long n = n_uniform + n_fg;
-  if (n == 0) return RM_OK;
-  if (num_src == 0 || num_src > INT32_MAX) return fail(ctx, RM_ERR_INVALID_ARG, "num_src %lld out of [1, 2^31)", (long long)num_src);
-  if (n_fg > 0 && (num_fg == 0 || !fg_indices)) return fail(ctx, RM_ERR_INVALID_ARG, "n_fg > 0 needs foreground indices");
-  if ((out_org && !ray_org) || (out_dir && !ray_dir) || (out_targets && !targets))
-    return fail(ctx, RM_ERR_INVALID_ARG, "an output is requested without its source array");
-  if (!out_org && !out_dir && !out_targets && !indices_out) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
-  const unsigned long long key = sample_key(seed, stream, counter);
-  hipLaunchKernelGGL(rm::rm_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ray_org, ray_dir,
-                     targets, (long long)num_src, fg_indices, (long long)num_fg, (long long)n_uniform, n, key, out_org,
-                     out_dir, out_targets, indices_out);
-  RM_HIP(ctx, hipGetLastError());
-  return RM_OK;
-}
-
-void rm_scene_from_packed(const float* act, int32_t M, rm_scene* s) {
-  if (!s) return;
-  s->centers = act;
-  s->colors = act + 3 * M;
-  s->radius = act + 6 * M;
-  s->light_dir = act + 7 * M;
-  s->ambient = act + 7 * M + 3;
-  s->num_spheres = M;
-}
-
-void rm_grads_from_packed(float* g, int32_t M, rm_grads* o) {
-  if (!o) return;
-  o->centers = g;
-  o->colors = g + 3 * M;
-  o->radius = g + 6 * M;
-  o->light_dir = g + 7 * M;
-  o->ambient = g + 7 * M + 3;
-}
-
-int rm_optimizer_step_f16(rm_context* ctx, float* raw_packed, const float* grad_act_packed, float* adam_m,
-                          float* adam_v, int32_t num_spheres, int32_t step, float lr, float weight_decay,
-                          int32_t with_penalties, float* loss_penalty, float* act_out, uint16_t* colors_f16_out) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  if (!raw_packed || !grad_act_packed || !adam_m || !adam_v)
-    return fail(ctx, RM_ERR_INVALID_ARG, "NULL optimizer buffer");
-  if (num_spheres < 1 || num_spheres > RM_MAX_SPHERES) return fail(ctx, RM_ERR_INVALID_ARG, "bad num_spheres");
-  if (step < 1 && !ctx->sdev) return fail(ctx, RM_ERR_INVALID_ARG, "step counts from 1");
-  const int M = num_spheres;
-  const int n = 7 * M + 4;
-  const int nb = (n + 255) / 256;
-  const bool prepared = ctx->opt_prepared && ctx->prep_raw == raw_packed && ctx->prep_M == M &&
-                        ctx->prep_step == step && ctx->prep_pen == (with_penalties ? 1 : 0) &&
-                        ctx->prep_loss_penalty == loss_penalty && !ctx->sdev;
-  ctx->opt_prepared = false;
-  if (prepared) {  // the gradient-independent part ran in the sampled launch (rm_train_step_sampled_prepared)
-    hipLaunchKernelGGL(rm::rm_optimizer_post_small, dim3(1), dim3(256), 0, ctx->stream, raw_packed, grad_act_packed,
-                       adam_m, adam_v, M, lr, weight_decay, act_out, reinterpret_cast<_Float16*>(colors_f16_out),
-                       static_cast<const float*>(ctx->opt_pre));
-    RM_HIP(ctx, hipGetLastError());
-    return RM_OK;
-  }
-  if (M <= rm::kOptSmallMaxM && !env_is("RM_OPT_SMALL", '0')) {  // one block: snapshot, repulsion rows, update
-    hipLaunchKernelGGL(rm::rm_optimizer_small, dim3(1), dim3(256), 0, ctx->stream, raw_packed, grad_act_packed, adam_m,
-                       adam_v, M, step, lr, weight_decay, with_penalties ? 1 : 0, loss_penalty, act_out,
-                       reinterpret_cast<_Float16*>(colors_f16_out), ctx->sdev);
-    RM_HIP(ctx, hipGetLastError());
-    return RM_OK;
-  }
-  // workspace: snapshot of the pre-step params | repulsion rows [M][4] | penalty partials
-  const size_t need = ((size_t)n + 4 * (size_t)M + (size_t)nb + 64) * sizeof(float);
-  int rc = ensure_ws(ctx, std::max(ctx->ws_bytes, need));
-  if (rc != RM_OK) return rc;
-  float* snap = static_cast<float*>(ctx->ws);
-  float* pair = snap + n;
-  float* parts = loss_penalty ? pair + 4 * M : nullptr;
-  hipLaunchKernelGGL(rm::rm_penalty_pairs, dim3(M), dim3(256), 0, ctx->stream, raw_packed, M,
-                     with_penalties ? 1 : 0, snap, pair);
-  RM_HIP(ctx, hipGetLastError());
-  hipLaunchKernelGGL(rm::rm_optimizer_kernel, dim3(nb), dim3(256), 0, ctx->stream, snap, raw_packed,
-                     grad_act_packed, adam_m, adam_v, pair, M, step, lr, weight_decay, with_penalties ? 1 : 0, parts,
-                     act_out, reinterpret_cast<_Float16*>(colors_f16_out), ctx->sdev);
-  RM_HIP(ctx, hipGetLastError());
-  if (ctx->sdev) {
-    hipLaunchKernelGGL(rm::rm_step_advance, dim3(1), dim3(64), 0, ctx->stream, ctx->sdev);
-    RM_HIP(ctx, hipGetLastError());
-  }
-  if (loss_penalty) {
-    hipLaunchKernelGGL(rm::rm_sum_small, dim3(1), dim3(64), 0, ctx->stream, parts, nb, loss_penalty);
-    RM_HIP(ctx, hipGetLastError());
-  }
-  return RM_OK;
-}
-
-int rm_optimizer_step(rm_context* ctx, float* raw_packed, const float* grad_act_packed, float* adam_m,
-                      float* adam_v, int32_t num_spheres, int32_t step, float lr, float weight_decay,
-                      int32_t with_penalties, float* loss_penalty, float* act_out) {
-  return rm_optimizer_step_f16(ctx, raw_packed, grad_act_packed, adam_m, adam_v, num_spheres, step, lr, weight_decay,
-                               with_penalties, loss_penalty, act_out, nullptr);
-}
-
-int rm_train_step_camera_adam(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width,
-                              int32_t height, const float* targets, float progress, float inv_count,
-                              const rm_march* march, float* act_packed, float* grad_packed, float* raw_packed,
-                              float* adam_m, float* adam_v, int32_t num_spheres, int32_t step, float lr,
-                              float weight_decay, int32_t with_penalties, float* loss_sum, float* loss_penalty,
-                              uint16_t* colors_f16_out) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->opt_prepared = false;
-  if (!act_packed || !grad_packed || !raw_packed || !adam_m || !adam_v || !march)
-    return fail(ctx, RM_ERR_INVALID_ARG, "NULL model buffer");
-  if (num_spheres < 1 || num_spheres > RM_MAX_SPHERES) return fail(ctx, RM_ERR_INVALID_ARG, "bad num_spheres");
-  const bool f16 = (march->flags & RM_MARCH_COLOR_F16) != 0;
-  if (f16 != (colors_f16_out != nullptr))
-    return fail(ctx, RM_ERR_INVALID_ARG, "colors_f16_out goes with RM_MARCH_COLOR_F16 (and only with it)");
-  if (step < 1 && !ctx->sdev) return fail(ctx, RM_ERR_INVALID_ARG, "step counts from 1");
-  const int M = num_spheres;
-  rm_scene sc;
-  rm_scene_from_packed(act_packed, M, &sc);
-  if (f16) sc.colors = reinterpret_cast<const float*>(colors_f16_out);  // the fp16 colours the step renders
-  rm_grads gr;
-  rm_grads_from_packed(grad_packed, M, &gr);
-  Call c;
-  c.mode = kTrain;
-  c.cam = true;
-  c.cams = cams;
-  c.views = num_views;
-  c.W = width;
-  c.H = height;
-  c.targets = targets;
-  c.progress = progress;
-  c.inv_count = inv_count;
-  c.scene = &sc;
-  c.march = march;
-  c.grads = &gr;
-  c.loss_sum = loss_sum;
-  c.accumulate = 0;
-  const Call::Adam ad{raw_packed, adam_m, adam_v, act_packed, loss_penalty, reinterpret_cast<_Float16*>(colors_f16_out),
-                      step, with_penalties ? 1 : 0, lr, weight_decay};
-  c.adam = &ad;
-  ctx->adam_done = false;
-  int rc = run(ctx, c);
-  const bool done = ctx->adam_done;
-  ctx->adam_done = false;
-  if (rc != RM_OK || done) return rc;
-  // not fused (more than 64 spheres, the small-scene kernel, sub-launches): the optimizer call
-  return rm_optimizer_step_f16(ctx, raw_packed, grad_packed, adam_m, adam_v, M, step, lr, weight_decay,
-                               with_penalties, loss_penalty, act_packed, colors_f16_out);
-}
-
-}  // extern "C"
-
-namespace {
-
-// rm_sample_batch into the context's batch buffer, then rm_train_step on it: the separate-call
-// form of the sampled step (rm_train_iteration's and rm_train_step_sampled's other sizes)
-int sample_then_train(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets,
-                      int64_t num_src, const int32_t* fg_indices, int64_t num_fg, int64_t n_uniform, int64_t n_fg,
-                      uint64_t seed, uint64_t stream, uint64_t counter, float progress, float inv_count,
-                      const rm_scene* sc, const rm_march* march, const rm_grads* gr, float* loss_sum) {
-  const long long n = n_uniform + n_fg;
-  int rc;
-  if (n > 0) {
-    const size_t need = sizeof(float) * 9 * (size_t)n;
-    if (need > ctx->batch_bytes) {
-      if (ctx->batch) {
-        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        RM_HIP(ctx, hipFree(ctx->batch));
-        ctx->batch = nullptr;
-        ctx->batch_bytes = 0;
-      }
-      if (hipMalloc(&ctx->batch, need) != hipSuccess) return fail(ctx, RM_ERR_OOM, "batch buffer (%zu B)", need);
-      ctx->batch_bytes = need;
-    }
-  }
-  float* bo = ctx->batch;
-  float* bd = bo ? bo + 3 * n : nullptr;
-  float* bt = bo ? bo + 6 * n : nullptr;
-  if (n > 0 && (rc = rm_sample_batch(ctx, ray_org, ray_dir, targets, num_src, fg_indices, num_fg, n_uniform, n_fg, seed,
-                                     stream, counter, bo, bd, bt, nullptr)) != RM_OK)
-    return rc;
-  return rm_train_step(ctx, bo, bd, bt, n, progress, inv_count, sc, march, gr, loss_sum, nullptr, 0);
-}
-
-// the sampled step's validation (rm_train_iteration and rm_train_step_sampled)
-int check_sampling(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets,
-                   int64_t num_src, const int32_t* fg_indices, int64_t num_fg, int64_t n_uniform, int64_t n_fg) {
-  if (!ray_org || !ray_dir || !targets) return fail(ctx, RM_ERR_INVALID_ARG, "NULL dataset array");
-  if (num_src < 1 || num_src > INT32_MAX || n_uniform < 0 || n_fg < 0 || num_fg < 0)
-    return fail(ctx, RM_ERR_INVALID_ARG, "bad sampling sizes");
-  if (n_fg > 0 && (num_fg == 0 || !fg_indices)) return fail(ctx, RM_ERR_INVALID_ARG, "n_fg > 0 needs foreground indices");
-  return RM_OK;
-}
-
-// one launch of the small-scene kernel with its in-kernel final reduction for this call
-bool sampled_one_launch(const Call& c, int M, long long n) {
-  const int rpb = kBlock / small_lpr(c, n);
-  return use_small(c, M, n) && (n + rpb - 1) / rpb <= kSmallFinalMaxBlocks &&
-         (n + rpb - 1) / rpb <= max_blocks_per_launch() && !env_is("RM_FUSED_ITER", '0');
-}
-
-}  // namespace
-
-extern "C" {
-
-}  // extern "C"
-
-namespace {
-// rm_train_step_sampled[_prepared]; raw_packed != nullptr: prepare the next optimizer step
-int sampled_step(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets, int64_t num_src,
-                 const int32_t* fg_indices, int64_t num_fg, int64_t n_uniform, int64_t n_fg, uint64_t seed,
-                 uint64_t stream, uint64_t counter, float progress, float inv_count, const rm_scene* scene,
-                 const rm_march* march, const rm_grads* grads, float* loss_sum, const float* raw_packed, int32_t step,
-                 int32_t with_penalties, float* loss_penalty) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->opt_prepared = false;  // a preparation is for the optimizer call right after its own step
-  int rc;
-  if ((rc = check_sampling(ctx, ray_org, ray_dir, targets, num_src, fg_indices, num_fg, n_uniform, n_fg)) != RM_OK)
-    return rc;
-  if (!scene || !march || !grads) return fail(ctx, RM_ERR_INVALID_ARG, "NULL scene / march / grads");
-  if (scene->num_spheres < 1 || scene->num_spheres > RM_MAX_SPHERES) return fail(ctx, RM_ERR_INVALID_ARG, "bad num_spheres");
-  const long long n = n_uniform + n_fg;
-  Call c;
-  c.mode = kTrain;
-  c.cam = false;
-  c.org = ray_org;
-  c.dir = ray_dir;
-  c.n = n;
-  c.targets = targets;
-  c.progress = progress;
-  c.inv_count = inv_count;
-  c.scene = scene;
-  c.march = march;
-  c.grads = grads;
-  c.loss_sum = loss_sum;
-  c.accumulate = 0;
-  // one launch: the small kernel draws its rays and reduces the gradient in its last block
-  if (n > 0 && sampled_one_launch(c, scene->num_spheres, n) && ctx->sdev == nullptr) {
-    SmallArgs fz;
-    std::memset(&fz, 0, sizeof fz);
-    fz.src_org = ray_org;
-    fz.src_dir = ray_dir;
-    fz.src_tgt = targets;
-    fz.fg = fg_indices;
-    fz.num_src = num_src;
-    fz.num_fg = num_fg;
-    fz.n_uniform = n_uniform;
-    fz.key = sample_key(seed, stream, counter);
-    const int M = scene->num_spheres;
-    const bool prep = raw_packed != nullptr && M <= kOptSmallMaxM && !env_is("RM_OPT_SMALL", '0') &&
-                      !env_is("RM_OPT_PREPARE", '0');
-    fz.adam = prep ? 2 : 0;
-    if (prep) {  // the extra block: opt_small_pre of rm_optimizer_small on these parameters
-      fz.raw = const_cast<float*>(raw_packed);
-      fz.m1 = fz.m2 = const_cast<float*>(raw_packed);  // loaded with the parameters, not used
-      fz.step = step;
-      fz.with_pen = with_penalties ? 1 : 0;
-      fz.loss_penalty = loss_penalty;
-    }
-    c.fused = &fz;
-    rc = run(ctx, c);
-    if (rc == RM_OK && prep) {
-      ctx->opt_prepared = true;
-      ctx->prep_raw = raw_packed;
-      ctx->prep_loss_penalty = loss_penalty;
-      ctx->prep_M = M;
-      ctx->prep_step = step;
-      ctx->prep_pen = with_penalties ? 1 : 0;
-    }
-    return rc;
-  }
-  return sample_then_train(ctx, ray_org, ray_dir, targets, num_src, fg_indices, num_fg, n_uniform, n_fg, seed, stream,
-                           counter, progress, inv_count, scene, march, grads, loss_sum);
-}
-}  // namespace
-
-extern "C" {
-
-int rm_train_step_sampled(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets,
-                          int64_t num_src, const int32_t* fg_indices, int64_t num_fg, int64_t n_uniform,
-                          int64_t n_fg, uint64_t seed, uint64_t stream, uint64_t counter, float progress,
-                          float inv_count, const rm_scene* scene, const rm_march* march, const rm_grads* grads,
-                          float* loss_sum) {
-  return sampled_step(ctx, ray_org, ray_dir, targets, num_src, fg_indices, num_fg, n_uniform, n_fg, seed, stream,
-                      counter, progress, inv_count, scene, march, grads, loss_sum, nullptr, 0, 0, nullptr);
-}
-
-int rm_train_step_sampled_prepared(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets,
-                                   int64_t num_src, const int32_t* fg_indices, int64_t num_fg, int64_t n_uniform,
-                                   int64_t n_fg, uint64_t seed, uint64_t stream, uint64_t counter, float progress,
-                                   float inv_count, const rm_scene* scene, const rm_march* march,
-                                   const rm_grads* grads, float* loss_sum, const float* raw_packed, int32_t step,
-                                   int32_t with_penalties, float* loss_penalty) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  if (!raw_packed) return fail(ctx, RM_ERR_INVALID_ARG, "NULL raw parameters");
-  if (step < 1) return fail(ctx, RM_ERR_INVALID_ARG, "step counts from 1");
-  if (ctx->sdev) return fail(ctx, RM_ERR_INVALID_ARG, "prepared steps do not take bound step scalars");
-  return sampled_step(ctx, ray_org, ray_dir, targets, num_src, fg_indices, num_fg, n_uniform, n_fg, seed, stream,
-                      counter, progress, inv_count, scene, march, grads, loss_sum, raw_packed, step, with_penalties,
-                      loss_penalty);
-}
-
-int rm_train_iteration(rm_context* ctx, const float* ray_org, const float* ray_dir, const float* targets,
-                       int64_t num_src, const int32_t* fg_indices, int64_t num_fg, int64_t n_uniform, int64_t n_fg,
-                       uint64_t seed, uint64_t stream, uint64_t counter, float progress, float inv_count,
-                       const rm_march* march, float* act_packed, float* grad_packed, float* raw_packed,
-                       float* adam_m, float* adam_v, int32_t num_spheres, int32_t step, float lr,
-                       float weight_decay, int32_t with_penalties, float* loss_sum, float* loss_penalty) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  ctx->opt_prepared = false;
-  int rc;
-  if ((rc = check_sampling(ctx, ray_org, ray_dir, targets, num_src, fg_indices, num_fg, n_uniform, n_fg)) != RM_OK)
-    return rc;
-  if (!act_packed || !grad_packed || !raw_packed || !adam_m || !adam_v || !march)
-    return fail(ctx, RM_ERR_INVALID_ARG, "NULL model buffer");
-  if (num_spheres < 1 || num_spheres > RM_MAX_SPHERES) return fail(ctx, RM_ERR_INVALID_ARG, "bad num_spheres");
-  if ((march->flags & RM_MARCH_COLOR_F16) != 0)
-    return fail(ctx, RM_ERR_INVALID_ARG, "rm_train_iteration trains fp32 colour models");
-  if (step < 1 && !ctx->sdev) return fail(ctx, RM_ERR_INVALID_ARG, "step counts from 1");
-  const int M = num_spheres;
-  const long long n = n_uniform + n_fg;
-  rm_scene sc;
-  rm_scene_from_packed(act_packed, M, &sc);
-  rm_grads gr;
-  rm_grads_from_packed(grad_packed, M, &gr);
-  Call c;
-  c.mode = kTrain;
-  c.cam = false;
-  c.org = ray_org;
-  c.dir = ray_dir;
-  c.n = n;
-  c.targets = targets;
-  c.progress = progress;
-  c.inv_count = inv_count;
-  c.scene = &sc;
-  c.march = march;
-  c.grads = &gr;
-  c.loss_sum = loss_sum;
-  c.accumulate = 0;
-  // one launch: the small kernel with its in-kernel final reduction (RM_FUSED_ITER=0: three calls)
-  const bool fused = sampled_one_launch(c, M, n) && M <= kOptSmallMaxM && ctx->sdev == nullptr;
-  if (fused) {
-    SmallArgs fz;
-    std::memset(&fz, 0, sizeof fz);
-    fz.src_org = ray_org;
-    fz.src_dir = ray_dir;
-    fz.src_tgt = targets;
-    fz.fg = fg_indices;
-    fz.num_src = num_src;
-    fz.num_fg = num_fg;
-    fz.n_uniform = n_uniform;
-    fz.key = sample_key(seed, stream, counter);
-    fz.raw = raw_packed;
-    fz.m1 = adam_m;
-    fz.m2 = adam_v;
-    fz.step = step;
-    fz.with_pen = with_penalties ? 1 : 0;
-    fz.lr = lr;
-    fz.wd = weight_decay;
-    fz.loss_penalty = loss_penalty;
-    fz.act_out = act_packed;
-    fz.adam = 1;
-    c.fused = &fz;
-    return run(ctx, c);
-  }
-  // the same three steps as separate calls: draw + gather, train step, optimizer
-  if ((rc = sample_then_train(ctx, ray_org, ray_dir, targets, num_src, fg_indices, num_fg, n_uniform, n_fg, seed,
-                              stream, counter, progress, inv_count, &sc, march, &gr, loss_sum)) != RM_OK)
-    return rc;
-  return rm_optimizer_step(ctx, raw_packed, grad_packed, adam_m, adam_v, M, step, lr, weight_decay, with_penalties,
-                           loss_penalty, act_packed);
-}
-
-}  // extern "C"
-
-// ---- ray and camera-pose gradients (rm_raygrad.h) -------------------------------------------
-namespace {
-
-struct RayGradCall {
-  bool cam = false;
-  const float* org = nullptr;
-  const float* dir = nullptr;
-  long long n = 0;
-  const rm_camera* cams = nullptr;
-  int views = 0, W = 0, H = 0;
-  const rm_scene* scene = nullptr;
-  const rm_march* march = nullptr;
-  const float* gout = nullptr;
-  const float* t_in = nullptr;
-  float* g_org = nullptr;
-  float* g_dir = nullptr;
-  rm_camera* grad_cams = nullptr;
-  int accumulate = 0;
-};
-
-int run_raygrad(rm_context* ctx, const RayGradCall& c) {
-  if (!ctx) return RM_ERR_INVALID_ARG;
-  int rc;
-  if ((rc = check_scene(ctx, c.scene, true)) != RM_OK) return rc;
-  if ((rc = check_march(ctx, c.march)) != RM_OK) return rc;
-  if (c.cam) {
-    if (!c.cams) return fail(ctx, RM_ERR_INVALID_ARG, "cams is NULL");
-    if (c.views < 1 || c.views > RM_MAX_VIEWS_PER_CALL)
-      return fail(ctx, RM_ERR_INVALID_ARG, "num_views %d out of [1, %d]", c.views, RM_MAX_VIEWS_PER_CALL);
-    if (c.W < 1 || c.H < 1 || (long long)c.W * c.H > (1LL << 28))
-      return fail(ctx, RM_ERR_INVALID_ARG, "bad image size %dx%d", c.W, c.H);
-    if (!c.grad_cams) return fail(ctx, RM_ERR_INVALID_ARG, "grad_cams is NULL");
-  } else {
-    if (c.n < 0) return fail(ctx, RM_ERR_INVALID_ARG, "num_rays %lld < 0", c.n);
-    if (c.n > 0 && (!c.org || !c.dir)) return fail(ctx, RM_ERR_INVALID_ARG, "ray_org/ray_dir is NULL");
-    if (!c.g_org && !c.g_dir) return fail(ctx, RM_ERR_INVALID_ARG, "grad_org and grad_dir are both NULL");
-  }
-  const long long n = c.cam ? (long long)c.views * c.W * c.H : c.n;
-  if (n > 0 && !c.gout) return fail(ctx, RM_ERR_INVALID_ARG, "grad_out is NULL");
-  if (n == 0) return RM_OK;
-  const long long bpv = c.cam ? ((long long)c.W * c.H + kBlock - 1) / kBlock : 0;
-  if ((rc = ensure_rg(ctx, rg_need(n))) != RM_OK) return rc;
-
-  // no saved t: the existing forward replays the march into the workspace (escaped rays' t carries
-  // the documented guarantee); the gradient kernel itself never marches
-  const float* t_in = c.t_in;
-  if (!t_in) {
-    Call f;
-    f.mode = kFwd;
-    f.cam = c.cam;
-    f.org = c.org;
-    f.dir = c.dir;
-    f.n = c.n;
-    f.cams = c.cams;
-    f.views = c.views;
-    f.W = c.W;
-    f.H = c.H;
-    f.scene = c.scene;
-    f.march = c.march;
-    f.t_out = ctx->rg_ws;
-    if ((rc = run(ctx, f)) != RM_OK) return rc;
-    t_in = ctx->rg_ws;
-  }
-  ctx->opt_prepared = false;
-
-  const int M = c.scene->num_spheres, Mpad = pad_spheres(M);
-  KArgs a;
-  std::memset(&a, 0, sizeof a);
-  a.org = c.org;
-  a.dir = c.dir;
-  a.centers = c.scene->centers;
-  if ((c.march->flags & RM_MARCH_COLOR_F16) != 0) a.colors_h = reinterpret_cast<const _Float16*>(c.scene->colors);
-  else a.colors = c.scene->colors;
-  a.radius = c.scene->radius;
-  a.light_dir = c.scene->light_dir;
-  a.ambient = c.scene->ambient;
-  a.M = M;
-  a.Mpad = Mpad;
-  a.steps = c.march->steps;
-  a.k = c.march->smooth_k;
-  a.eps = c.march->normal_eps;
-  a.csharp = c.march->color_sharpness;
-  a.msharp = c.march->mask_sharpness;
-  a.gout = c.gout;
-  a.t_in = t_in;
-  a.lse_slack = (float)(std::log((double)M) / (double)a.k * (1.0 + 1e-6)) + 1e-7f;
-  a.rec = rec_floats(Mpad);
-  RayGradCams tail;
-  if (c.cam) {
-    if (c.views <= kInlineCams) {
-      for (int v = 0; v < c.views; ++v)
-        if ((rc = make_basis(ctx, c.cams[v], c.W, c.H, a.cams[v])) != RM_OK) return rc;
-    } else {
-      Call u;
-      u.mode = kBwd;
-      u.cam = true;
-      u.cams = c.cams;
-      u.views = c.views;
-      u.W = c.W;
-      u.H = c.H;
-      if ((rc = upload_cams(ctx, u, a)) != RM_OK) return rc;
-    }
-    a.width = c.W;
-    a.height = c.H;
-    a.num_views = c.views;
-    a.tiling = (c.W % 16 == 0 && c.H % 16 == 0 && (c.march->flags & RM_MARCH_ROW_ORDER) == 0) ? 2 : 0;
-    std::memset(&tail, 0, sizeof tail);
-    for (int v = 0; v < c.views; ++v) tail.c[v] = c.cams[v];
-  }
-  // sphere records of this call (rm_prep_kernel; fp16 colours are widened there)
-  {
-    const int np = Mpad / 2, nprep = (np + 255) / 256;
-    const size_t need = rec_bytes(np, nprep);
-    if (need > ctx->rec_bytes) {
-      if (ctx->rec) {
-        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        RM_HIP(ctx, hipFree(ctx->rec));
-        ctx->rec = nullptr;
-        ctx->rec_bytes = 0;
-      }
-      if (hipMalloc(&ctx->rec, need) != hipSuccess) return fail(ctx, RM_ERR_OOM, "record buffer (%zu B)", need);
-      ctx->rec_bytes = need;
-    }
-    hipLaunchKernelGGL(rm_prep_kernel, dim3(nprep), dim3(256), 0, ctx->stream, a, (float4*)ctx->rec);
-    RM_HIP(ctx, hipGetLastError());
-    if (nprep > 1) {
-      float* hdr = reinterpret_cast<float*>((char*)ctx->rec + (size_t)np * (7 * 16 + 8));
-      float* esc = reinterpret_cast<float*>((char*)ctx->rec + esc_offset(np, nprep));
-      hipLaunchKernelGGL(rm_prep_finish, dim3(1), dim3(256), 0, ctx->stream, a, hdr, esc, nprep);
-      RM_HIP(ctx, hipGetLastError());
-    }
-    a.rec_buf = (const float4*)ctx->rec;
-  }
-  RayGradArgs r{};
-  r.g_org = c.g_org;
-  r.g_dir = c.g_dir;
-  r.accumulate = c.accumulate ? 1 : 0;
-  hipEvent_t ev0, ev1;
-  if (c.cam) {
-    // the partial rows follow the t of all n rays (the replayed march may live there)
-    r.partial = ctx->rg_ws + n;
-    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
-    hipExtLaunchKernelGGL((rm_raygrad_kernel<true>), dim3((unsigned)bpv, (unsigned)c.views), dim3(kBlock), 0,
-                          ctx->stream, ev0, ev1, 0u, a, r);
-    RM_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(rm_raygrad_finish, dim3((unsigned)c.views), dim3(256), 0, ctx->stream, r.partial, (int)bpv, tail,
-                       reinterpret_cast<float*>(c.grad_cams), r.accumulate);
-    RM_HIP(ctx, hipGetLastError());
-    return RM_OK;
-  }
-  for (long long done = 0; done < n;) {
-    const long long nb = std::min<long long>((n - done + kBlock - 1) / kBlock, max_blocks_per_launch());
-    const long long nr = std::min<long long>(n - done, nb * kBlock);
-    a.ray_begin = done;
-    a.n_rays = nr;
-    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
-    hipExtLaunchKernelGGL((rm_raygrad_kernel<false>), dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream, ev0, ev1, 0u,
-                          a, r);
-    RM_HIP(ctx, hipGetLastError());
-    done += nr;
-  }
-  return RM_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rm_render_diff_backward_rays(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
-                                 const rm_scene* scene, const rm_march* march, const float* grad_out,
-                                 const float* t_march, float* grad_org, float* grad_dir, int32_t accumulate) {
-  RayGradCall c;
-  c.cam = false;
-  c.org = ray_org;
-  c.dir = ray_dir;
-  c.n = num_rays;
-  c.scene = scene;
-  c.march = march;
-  c.gout = grad_out;
-  c.t_in = t_march;
-  c.g_org = grad_org;
-  c.g_dir = grad_dir;
-  c.accumulate = accumulate;
-  return run_raygrad(ctx, c);
-}
-
-int rm_render_diff_backward_cameras(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width,
-                                    int32_t height, const rm_scene* scene, const rm_march* march,
-                                    const float* grad_out, const float* t_march, rm_camera* grad_cams,
-                                    int32_t accumulate) {
-  RayGradCall c;
-  c.cam = true;
-  c.cams = cams;
-  c.views = num_views;
-  c.W = width;
-  c.H = height;
-  c.scene = scene;
-  c.march = march;
-  c.gout = grad_out;
-  c.t_in = t_march;
-  c.grad_cams = grad_cams;
-  c.accumulate = accumulate;
-  return run_raygrad(ctx, c);
-}
-
-}  // extern "C"
+#include "rm_context.h"
+#include "rm_launch.h"
+#include "rm_api.h"
