@@ -754,23 +754,32 @@ __device__ __forceinline__ void lse_point(const float p[3], const Lds& L, int np
 // lane l the ray of lane l mod 16 NCB; only the first NCB column blocks are multiplied and summed,
 // and the reduction takes the missing blocks as copies of the present ones. A ray's sum is the
 // same chain of the same terms as with NCB = 4 (the same bits; IEEE addition is commutative).
-template <bool CLAMP, bool FIXED, int NCB = 4>
+// PACK (the unsplit march's packed step, lse_mfma_packed): only the lanes with `live` set need
+// their sum. Live lane l writes its ray into column `slot` = its rank among the live lanes, so
+// the live rays fill the first NCB = ceil(live / 16) column blocks and only those are multiplied;
+// the missing blocks add 0 to the reduction, which leaves lane s with the total of column s, and a
+// live lane fetches its own from lane `slot`. The other lanes write nothing (the columns past the
+// last live one hold stale fragments; a column touches no other column) and get no meaningful sum.
+template <bool CLAMP, bool FIXED, int NCB = 4, bool PACK = false>
 __device__ __forceinline__ float lse_mfma(const float p[3], float k2, float sh, const uint4* __restrict__ At,
                                           const float* __restrict__ Wt, int nrb, uint4* xa, uint4* xb, float* xs,
-                                          int lane) {
+                                          int lane, int slot = 0, bool live = true) {
   // no fp contraction: the record kernel's origin step (write_origins) runs this code in another
   // kernel and must reproduce it bit for bit
 #pragma clang fp contract(off)
-  static_assert(NCB == 1 || NCB == 2 || NCB == 4, "column blocks per wave");
+  static_assert(PACK ? NCB >= 1 && NCB <= 3 : NCB == 1 || NCB == 2 || NCB == 4, "column blocks per wave");
   {  // the lane's own ray: Sa, Sb and the shift into the exchange
     unsigned x[3], y[3], z[3], P[3];
     split3(p[0], x[0], x[1], x[2]);
     split3(p[1], y[0], y[1], y[2]);
     split3(p[2], z[0], z[1], z[2]);
     split3(k2 * psq(p), P[0], P[1], P[2]);
-    xa[lane] = make_uint4(pack2(x[0], x[1]), pack2(x[2], y[0]), pack2(y[1], y[2]), pack2(z[0], z[1]));
-    xb[lane] = make_uint4(pack2(z[2], z[2]), pack2(P[0], P[1]), pack2(P[2], kBf16One), pack2(kBf16One, kBf16One));
-    if constexpr (FIXED) xs[lane] = sh;
+    const int col = PACK ? slot : lane;
+    if (!PACK || live) {
+      xa[col] = make_uint4(pack2(x[0], x[1]), pack2(x[2], y[0]), pack2(y[1], y[2]), pack2(z[0], z[1]));
+      xb[col] = make_uint4(pack2(z[2], z[2]), pack2(P[0], P[1]), pack2(P[2], kBf16One), pack2(kBf16One, kBf16One));
+      if constexpr (FIXED) xs[col] = sh;
+    }
   }
   __builtin_amdgcn_wave_barrier();
   const int n = lane & 15, g = lane >> 4;
@@ -854,12 +863,33 @@ __device__ __forceinline__ float lse_mfma(const float p[3], float k2, float sh, 
   // the blocks 1/3, then each row adds its bit-4 partner
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) acc[cb] = acc2[cb].x + acc2[cb].y;
-  // NCB < 4: column block cb + NCB is a copy of block cb (the lanes' rays repeat every 16 NCB)
+  // NCB < 4: column block cb + NCB is a copy of block cb (the lanes' rays repeat every 16 NCB);
+  // PACK: the blocks not multiplied add 0
 #pragma unroll
-  for (int cb = NCB; cb < 4; ++cb) acc[cb] = acc[cb - NCB];
+  for (int cb = NCB; cb < 4; ++cb) acc[cb] = PACK ? 0.0f : acc[cb - NCB];
   const float own = swap16_sum(swap32_sum(acc[0], acc[2]), swap32_sum(acc[1], acc[3]));
   __builtin_amdgcn_wave_barrier();  // the exchange is rewritten by the next step
+  if constexpr (PACK) return u2f(__builtin_amdgcn_ds_bpermute(slot << 2, f2u(own)));  // column `slot`'s total
   return own;
+}
+
+// The unsplit march's step on the matrix cores for the `live` lanes only (bm = their ballot): the
+// live rays packed into ncb = ceil(popc(bm) / 16) column blocks (lse_mfma, PACK), one loop per
+// block count chosen by a scalar switch. More than 48 live rays need all four blocks: the wave
+// runs the unpacked step, every lane in its own column (no rank, no fetch; the lanes that are not
+// live get their sum as well). ncb == 0: no tile at all. A ray's sum does not depend on its
+// column, so a live lane gets the bits of the unpacked step.
+template <bool CLAMP, bool FIXED>
+__device__ __forceinline__ float lse_mfma_packed(const float p[3], float k2, float sh, const uint4* __restrict__ At,
+                                                 const float* __restrict__ Wt, int nrb, uint4* xa, uint4* xb,
+                                                 float* xs, int lane, unsigned long long bm, bool live) {
+  const int ncb = (__popcll(bm) + 15) >> 4;
+  if (ncb == 4) return lse_mfma<CLAMP, FIXED, 4>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane);
+  if (ncb == 0) return 0.0f;
+  const int slot = __builtin_amdgcn_mbcnt_hi((unsigned)(bm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bm, 0u));
+  if (ncb == 1) return lse_mfma<CLAMP, FIXED, 1, true>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane, slot, live);
+  if (ncb == 2) return lse_mfma<CLAMP, FIXED, 2, true>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane, slot, live);
+  return lse_mfma<CLAMP, FIXED, 3, true>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane, slot, live);
 }
 
 // Split march (RM_MARCH_SPLIT): the kSplitWaves waves of a block hold the same 64 rays; wave w
@@ -878,13 +908,18 @@ __device__ __forceinline__ float split_combine(float part, float* comb, int wave
 // A march step's soft-min D at p on the matrix cores without a shift (soft_min_march's
 // unshifted step; shared with write_origins like march_d_fixed). comb != nullptr: a split
 // block's wave, At / Wt / nrb its quarter (split_combine).
-template <bool CLAMP, int NCB = 4>
+// PACK: the unsplit march's packed step (lse_mfma_packed) for the lanes with `live` set.
+template <bool CLAMP, int NCB = 4, bool PACK = false>
 __device__ __forceinline__ float march_d_none(const float p[3], float kappa, float inv_kappa,
                                               const uint4* __restrict__ At, const float* __restrict__ Wt, int nrb,
                                               uint4* xa, uint4* xb, float* xs, int lane, float* comb = nullptr,
-                                              int wave = 0) {
+                                              int wave = 0, unsigned long long bm = 0, bool live = true) {
 #pragma clang fp contract(off)
-  float s = lse_mfma<CLAMP, false, NCB>(p, kappa * kappa, 0.0f, At, Wt, nrb, xa, xb, xs, lane);
+  float s;
+  if constexpr (PACK)
+    s = lse_mfma_packed<CLAMP, false>(p, kappa * kappa, 0.0f, At, Wt, nrb, xa, xb, xs, lane, bm, live);
+  else
+    s = lse_mfma<CLAMP, false, NCB>(p, kappa * kappa, 0.0f, At, Wt, nrb, xa, xb, xs, lane);
   if (comb != nullptr) s = split_combine(s, comb, wave, lane);
   return -flog2(fmaxf(s, 1e-30f)) * inv_kappa;
 }
@@ -900,15 +935,20 @@ __device__ __forceinline__ float fixed_shift(const float p[3], float k2, const f
 // A march step's soft-min D at p on the matrix cores with the fixed shift sh = rho'_0 (sphere 0;
 // S00 / S10 = its records S0[0] / S1[0]) -- soft_min_march's fixed-shift step, shared with the
 // per-view origin step (write_origins) so that both give the same bits.
-template <bool CLAMP, int NCB = 4>
+template <bool CLAMP, int NCB = 4, bool PACK = false>
 __device__ __forceinline__ float march_d_fixed(const float p[3], float kappa, float inv_kappa, float kr_first,
                                                const float4& S00, const float4& S10, const uint4* __restrict__ At,
                                                const float* __restrict__ Wt, int nrb, uint4* xa, uint4* xb,
-                                               float* xs, int lane, float* comb = nullptr, int wave = 0) {
+                                               float* xs, int lane, float* comb = nullptr, int wave = 0,
+                                               unsigned long long bm = 0, bool live = true) {
 #pragma clang fp contract(off)
   const float k2 = kappa * kappa;
   const float sh = fixed_shift(p, k2, S00, S10);
-  float s = lse_mfma<CLAMP, true, NCB>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane);
+  float s;
+  if constexpr (PACK)
+    s = lse_mfma_packed<CLAMP, true>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane, bm, live);
+  else
+    s = lse_mfma<CLAMP, true, NCB>(p, k2, sh, At, Wt, nrb, xa, xb, xs, lane);
   if (comb != nullptr) s = split_combine(s, comb, wave, lane);
   const float m = kr_first - sh;
   return -(flog2(fmaxf(s, 1e-30f)) + m) * inv_kappa;
@@ -1643,10 +1683,18 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   // fixed clamped), shader cycles inside the matrix-core steps, vector-path steps
   unsigned long long tr_paths = 0, tr_lse_cyc = 0, tr_vec = 0;
 #endif
+  // What the unsplit march's packed step reads of the march's state (see the march): the ray's t
+  // now, one and two steps back (the cycle exit's history), the D of the step two back (Dprev is
+  // the D one step back) and the wave's choice history.
+  struct Memo {
+    float t, t1, t2, D2;
+    int chist;
+  };
+  int skipped_cb = 0;  // wave-uniform: column blocks the packed steps did not multiply (work statistics)
   // choice: the step's wave-uniform choices, bit 0 unshifted, bit 1 fixed shift, bit 2 clamp-free
   // force: 0 the cheapest safe shift for the wave (above); 1 the fixed shift, 2 the running maximum,
   // 3 unshifted (ray mode: see soft_min_march)
-  auto soft_min_core = [&](const float p[3], bool fast, float Dprev, int& choice, int force) {
+  auto soft_min_core = [&](const float p[3], bool fast, float Dprev, int& choice, int force, const Memo& mm) {
     bool none = force == 3 || (force == 0 && shift_none_ok &&
                 __all(2.0f * fmaxf(Dprev, 0.0f) + a.lse_slack <= 90.0f * inv_kappa || gone));
     // or: the nearest sphere is no farther than sphere 0, k (rho_0 - r_0) = rho'_0 - k r_0 <= 90
@@ -1682,7 +1730,35 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
         comb = L.slots + kSplitCombOff + (split_par ^= 1) * (kWaves * 64);
       }
       constexpr int kNcb = SPLIT ? kSplitCB : 4;  // column blocks of this wave's rays
-      if (fixed) {  // the ray's shift: rho'_0 of sphere 0 (any value near it keeps +-100 headroom)
+      if (!SPLIT && a.early_exit) {
+        // Packed step (exact). A step's D is a function of the ray's t and the step's shift form
+        // (choice & 3; the clamp bit changes no bit), so a ray whose t equals its t one or two steps
+        // back, under the form of that step, has the D of that step: it is known, not summed again
+        // (hit rays settle into a period-1 or period-2 cycle long before their wave does). The
+        // choice above came from every ray's own votes as before. Only the live rays -- not gone
+        // (their D is unused), not known -- are summed, packed into ceil(live / 16) column blocks.
+        // Lanes past n_rays are copies of ray 0 that vote like rays: they stay in. Exit off: the
+        // unpacked step below (every ray does every step's work), so exit on == off tests the bits
+        // of the memo and of the packing. Render mode keeps no history: no ray is ever known there.
+        const int form = choice & 3;
+        const bool memo = MODE != kRender;
+        const bool known2 = memo && mm.t == mm.t2 && form == ((mm.chist >> 3) & 3);
+        const bool known1 = memo && mm.t == mm.t1 && form == (mm.chist & 3);
+        const bool live = !gone && !known1 && !known2;
+        const unsigned long long bm = __ballot(live);
+        skipped_cb += 4 - ((__popcll(bm) + 15) >> 4);
+        if (fixed) {
+          const float4 A = Lds::v4(L.S0[0]), B = Lds::v4(L.S1[0]);
+          Dm = fast ? march_d_fixed<false, 4, true>(p, kappa, inv_kappa, kr_first, A, B, At, Wt, nq, xa, xb, xs, lane,
+                                                    nullptr, 0, bm, live)
+                    : march_d_fixed<true, 4, true>(p, kappa, inv_kappa, kr_first, A, B, At, Wt, nq, xa, xb, xs, lane,
+                                                   nullptr, 0, bm, live);
+        } else {
+          Dm = fast ? march_d_none<false, 4, true>(p, kappa, inv_kappa, At, Wt, nq, xa, xb, xs, lane, nullptr, 0, bm, live)
+                    : march_d_none<true, 4, true>(p, kappa, inv_kappa, At, Wt, nq, xa, xb, xs, lane, nullptr, 0, bm, live);
+        }
+        Dm = known2 ? mm.D2 : (known1 ? Dprev : Dm);
+      } else if (fixed) {  // the ray's shift: rho'_0 of sphere 0 (any value near it keeps +-100 headroom)
         const float4 A = Lds::v4(L.S0[0]), B = Lds::v4(L.S1[0]);
         Dm = fast ? march_d_fixed<false, kNcb>(p, kappa, inv_kappa, kr_first, A, B, At, Wt, nq, xa, xb, xs, lane, comb, wave)
                   : march_d_fixed<true, kNcb>(p, kappa, inv_kappa, kr_first, A, B, At, Wt, nq, xa, xb, xs, lane, comb, wave);
@@ -1731,7 +1807,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   // it (|p| <= 1e5, the fixed form's fp32 headroom), else the running maximum (a vector sweep over
   // all spheres, lane by lane); a wave runs each form only when one of its live rays takes it
   // (two forms in the waves whose rays disagree).
-  auto soft_min_march = [&](const float p[3], bool fast, float Dprev, int& choice) {
+  auto soft_min_march = [&](const float p[3], bool fast, float Dprev, int& choice, const Memo& mm) {
     if constexpr (SPLIT) {
       const bool live = !gone && !retired;
       bool nr = live && shift_none_ok && 2.0f * fmaxf(Dprev, 0.0f) + a.lse_slack <= 90.0f * inv_kappa;
@@ -1746,13 +1822,13 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       if (!a.early_exit && (bn | bf | bx) == 0ull) bn = 1ull;
       int cm = 0;
       float Dn = 0.0f, Dm = 0.0f, Dx = 0.0f;
-      if (bn != 0ull) Dn = soft_min_core(p, fast, Dprev, cm, 3);
-      if (bf != 0ull) Dm = soft_min_core(p, fast, Dprev, cm, 1);
-      if (bx != 0ull) Dx = soft_min_core(p, fast, Dprev, cm, 2);
+      if (bn != 0ull) Dn = soft_min_core(p, fast, Dprev, cm, 3, mm);
+      if (bf != 0ull) Dm = soft_min_core(p, fast, Dprev, cm, 1, mm);
+      if (bx != 0ull) Dx = soft_min_core(p, fast, Dprev, cm, 2, mm);
       choice = (nr ? 1 : 0) | (use_fixed ? 2 : 0) | (fast ? 4 : 0);
       return nr ? Dn : (use_fixed ? Dm : Dx);
     } else {
-      return soft_min_core(p, fast, Dprev, choice, 0);
+      return soft_min_core(p, fast, Dprev, choice, 0, mm);
     }
   };
 
@@ -1844,6 +1920,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // the latest in the low bits; 7 is no valid choice)
     float cyc_t1 = __builtin_nanf(""), cyc_t2 = __builtin_nanf("");
     int chist = 0xFFF;
+    float Dprev2 = INFINITY;  // the D two steps back (the packed step's memo)
     int rhist = 0xFFF;  // ray mode: the ray's own choice history (per lane: listed rays come from many groups)
     if (SPLIT && a.cont_resume > 0) {  // the state the first launch saved at step cont_resume
       const float* cs = a.cont_state;
@@ -1911,7 +1988,8 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
         break;
       }
       int choice;
-      const float D = soft_min_march(p, all_safe(lb, rho_lb), Dprev, choice);
+      const Memo mm{t, cyc_t1, cyc_t2, Dprev2, chist};
+      const float D = soft_min_march(p, all_safe(lb, rho_lb), Dprev, choice, mm);
       const float t_step = t;  // this step's state: (t_step, choice)
       if constexpr (SPLIT) {
         // Ray mode: a ray's step is a function of its own t (the shift is scene-uniform; the clamp
@@ -1957,6 +2035,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       rho_lb = rho_moved(rho_lb, t_step, t);
       // next point: hard min >= soft-min D here, moved by |D|
       lb = D - fabsf(D);
+      Dprev2 = Dprev;
       Dprev = D;
       // Cycle exit (exact). A march step is a deterministic function of the wave's state: the t
       // of every ray that is not gone and the step's wave-uniform choice (which carries all the
@@ -1995,6 +2074,9 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
         chist = ((chist << 3) | choice) & 0xFFF;
       }
     }
+    // the column blocks the packed steps did not multiply, in whole steps of the wave (four
+    // blocks), rounded down: the work counters keep counting executed lane work
+    if constexpr (!SPLIT) steps_saved += skipped_cb >> 2;
     if (SPLIT && a.ray_cont) {
       // ray mode: the listed rays' final states back into their groups' rows (the resume launch
       // runs the groups' post-march forward and backward); the steps this block ran uncounted
