@@ -526,6 +526,79 @@ int rmh_preview(const char* scene_json, const char* png_path, int32_t W, int32_t
   return rmh_image_save(png_path, host.data(), W, H);
 }
 
+void rmh_view_camera(const float pos[3], float yaw, float pitch, rmh_view_pose* out) {
+  if (!pos || !out) return;
+  // viewer.rs:65-86 in f64, rounded once (cos(pi/2) must not leak 6e-17 into a unit vector's f32)
+  auto normalize = [](double v[3]) {
+    const double len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    for (int k = 0; k < 3; ++k) v[k] /= len;
+  };
+  double f[3] = {std::cos((double)yaw) * std::cos((double)pitch), std::sin((double)pitch),
+                 std::sin((double)yaw) * std::cos((double)pitch)};
+  normalize(f);
+  double r[3] = {-f[2], 0.0, f[0]};  // forward x (0, 1, 0)
+  normalize(r);
+  double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
+  normalize(u);
+  for (int k = 0; k < 3; ++k) {
+    out->pos[k] = pos[k];
+    out->forward[k] = (float)f[k];
+    out->up[k] = (float)u[k];
+  }
+}
+
+int rmh_view(const char* scene_json, const char* out_pattern, int32_t W, int32_t H, const rmh_view_pose* cams,
+             int32_t count, float radius_offset, int32_t device) {
+  static_assert(sizeof(rmh_view_pose) == sizeof(rm_view_camera), "rmh_view_pose is rm_view_camera");
+  if (!scene_json || !out_pattern || !cams || W < 1 || H < 1 || count < 1)
+    return fail(RMH_ERR_INVALID_ARG, "bad arguments");
+  int32_t M = 0;
+  float *c = nullptr, *col = nullptr, *r = nullptr, ld[3], amb = 0.0f;
+  int rc = rmh_scene_load(scene_json, &M, &c, &col, &r, ld, &amb);
+  if (rc) return rc;
+  std::unique_ptr<float, void (*)(void*)> g1(c, std::free), g2(col, std::free), g3(r, std::free);
+  if (M < 1) return fail(RMH_ERR_FORMAT, "%s has no sphere", scene_json);
+  std::vector<float> act(7 * (size_t)M + 4);
+  std::memcpy(act.data(), c, sizeof(float) * 3 * M);
+  std::memcpy(act.data() + 3 * M, col, sizeof(float) * 3 * M);
+  for (int32_t i = 0; i < M; ++i) act[6 * M + i] = r[i] + radius_offset;  // viewer.rs draws the stored radii
+  std::memcpy(act.data() + 7 * M, ld, sizeof ld);
+  act[7 * M + 3] = amb;
+  Gpu g;
+  if ((rc = g.open(device)) != RMH_OK) return rc;
+  DevBuf d_act, out;
+  HIPCHK(d_act.alloc(sizeof(float) * act.size()));
+  HIPCHK(hipMemcpyAsync(d_act.p, act.data(), d_act.bytes, hipMemcpyHostToDevice, g.stream));
+  rm_scene sc;
+  rm_scene_from_packed(d_act.f(), M, &sc);
+  const size_t per_frame = 4 * (size_t)W * H;
+  const int32_t chunk_max = std::min<int32_t>(count, RM_MAX_VIEWS_PER_CALL);
+  HIPCHK(out.alloc(per_frame * chunk_max));
+  std::vector<uint8_t> host(per_frame * chunk_max);
+  const std::string pat = out_pattern;
+  const bool has_index = pat.find("%d") != std::string::npos;
+  for (int32_t f0 = 0; f0 < count; f0 += chunk_max) {
+    const int32_t nf = std::min(chunk_max, count - f0);
+    RMCHK(g.ctx, rm_view(g.ctx, reinterpret_cast<const rm_view_camera*>(cams + f0), nf, W, H, &sc, nullptr, nullptr,
+                         (uint8_t*)out.p, nullptr));
+    HIPCHK(hipMemcpyAsync(host.data(), out.p, per_frame * nf, hipMemcpyDeviceToHost, g.stream));
+    HIPCHK(hipStreamSynchronize(g.stream));
+    for (int32_t f = 0; f < nf; ++f) {
+      std::string path = pat;
+      const std::string idx = std::to_string(f0 + f);
+      if (has_index) {
+        path.replace(path.find("%d"), 2, idx);
+      } else if (count > 1) {
+        const size_t dot = path.rfind('.'), slash = path.rfind('/');
+        const size_t at = (dot == std::string::npos || (slash != std::string::npos && dot < slash)) ? path.size() : dot;
+        path.insert(at, "_" + idx);
+      }
+      if ((rc = rmh_png_write_rgba(path.c_str(), host.data() + per_frame * f, W, H)) != RMH_OK) return rc;
+    }
+  }
+  return RMH_OK;
+}
+
 int rmh_generate(const char* out_dir, const char* prefix, int32_t W, int32_t H, int32_t device) {
   if (!out_dir || W < 1 || H < 1) return fail(RMH_ERR_INVALID_ARG, "bad arguments");
   const std::string pre = prefix ? prefix : "";

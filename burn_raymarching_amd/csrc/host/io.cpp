@@ -383,7 +383,8 @@ const char* rmh_version(void) { return "burn_raymarching_amd host 0.1.0 src " RM
 
 void rmh_free(void* p) { std::free(p); }
 
-int rmh_png_read(const char* path, int32_t* width, int32_t* height, uint8_t** rgb) {
+// nch = 3: RGB8 out; 4: RGBA8 out (alpha 255 where the file has none)
+static int png_read_n(const char* path, int32_t* width, int32_t* height, uint8_t** rgb, int nch) {
   if (!path || !width || !height || !rgb) return fail(RMH_ERR_INVALID_ARG, "NULL argument");
   std::string f;
   if (!read_file(path, f)) return fail(RMH_ERR_IO, "cannot read %s", path);
@@ -462,37 +463,48 @@ int rmh_png_read(const char* path, int32_t* width, int32_t* height, uint8_t** rg
       row[x] = (unsigned char)v;
     }
   }
-  uint8_t* o = (uint8_t*)std::malloc((size_t)w * h * 3);
-  if (!o) return fail(RMH_ERR_IO, "out of host memory");
+  uint8_t* out = (uint8_t*)std::malloc((size_t)w * h * nch);
+  if (!out) return fail(RMH_ERR_IO, "out of host memory");
   for (size_t i = 0; i < (size_t)w * h; ++i) {
     const unsigned char* s = px.data() + i * ch;
+    uint8_t* o = out + (size_t)nch * i;
+    if (nch == 4) o[3] = ctype == 4 ? s[1] : (ctype == 6 ? s[3] : 255);
     switch (ctype) {
       case 0:
-      case 4: o[3 * i] = o[3 * i + 1] = o[3 * i + 2] = s[0]; break;
+      case 4: o[0] = o[1] = o[2] = s[0]; break;
       case 2:
-      case 6: o[3 * i] = s[0]; o[3 * i + 1] = s[1]; o[3 * i + 2] = s[2]; break;
+      case 6: o[0] = s[0]; o[1] = s[1]; o[2] = s[2]; break;
       case 3: {
         const size_t k = 3 * (size_t)s[0];
         if (k + 2 >= plte.size()) {
-          std::free(o);
+          std::free(out);
           return fail(RMH_ERR_FORMAT, "%s: palette index out of range", path);
         }
-        o[3 * i] = plte[k];
-        o[3 * i + 1] = plte[k + 1];
-        o[3 * i + 2] = plte[k + 2];
+        o[0] = plte[k];
+        o[1] = plte[k + 1];
+        o[2] = plte[k + 2];
         break;
       }
     }
   }
   *width = (int32_t)w;
   *height = (int32_t)h;
-  *rgb = o;
+  *rgb = out;
   return RMH_OK;
 }
 
-int rmh_png_write(const char* path, const uint8_t* rgb, int32_t width, int32_t height) {
+int rmh_png_read(const char* path, int32_t* width, int32_t* height, uint8_t** rgb) {
+  return png_read_n(path, width, height, rgb, 3);
+}
+
+int rmh_png_read_rgba(const char* path, int32_t* width, int32_t* height, uint8_t** rgba) {
+  return png_read_n(path, width, height, rgba, 4);
+}
+
+// nch = 3: RGB8 in (colour type 2); 4: RGBA8 in (colour type 6)
+static int png_write_n(const char* path, const uint8_t* rgb, int32_t width, int32_t height, int nch) {
   if (!path || !rgb || width < 1 || height < 1) return fail(RMH_ERR_INVALID_ARG, "bad PNG write arguments");
-  const size_t stride = (size_t)width * 3;
+  const size_t stride = (size_t)width * nch;
   std::string raw;
   raw.reserve((stride + 1) * height);
   for (int32_t y = 0; y < height; ++y) {
@@ -508,12 +520,20 @@ int rmh_png_write(const char* path, const uint8_t* rgb, int32_t width, int32_t h
   std::string ihdr;
   put_be32(ihdr, (uint32_t)width);
   put_be32(ihdr, (uint32_t)height);
-  ihdr += std::string("\x08\x02\x00\x00\x00", 5);  // 8-bit RGB, deflate, adaptive, no interlace
+  ihdr += std::string(nch == 4 ? "\x08\x06\x00\x00\x00" : "\x08\x02\x00\x00\x00", 5);  // 8-bit RGB[A], deflate, adaptive, no interlace
   put_chunk(o, "IHDR", ihdr);
   put_chunk(o, "IDAT", z);
   put_chunk(o, "IEND", std::string());
   if (!write_file(path, o)) return fail(RMH_ERR_IO, "cannot write %s", path);
   return RMH_OK;
+}
+
+int rmh_png_write(const char* path, const uint8_t* rgb, int32_t width, int32_t height) {
+  return png_write_n(path, rgb, width, height, 3);
+}
+
+int rmh_png_write_rgba(const char* path, const uint8_t* rgba, int32_t width, int32_t height) {
+  return png_write_n(path, rgba, width, height, 4);
 }
 
 void rmh_srgb8_to_linear(const uint8_t* in, int64_t n, float* out) {

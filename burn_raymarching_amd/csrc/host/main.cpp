@@ -19,10 +19,14 @@
 //   rm_train generate [--out data] [--prefix data/] [--size 256x256] [--device 0]
 //   rm_train preview  --scene scene.json --png out.png [--size 256x256]
 //                     [--eye 0,0,-2.5] [--target 0,0,0] [--fov 50] [--radius-offset 0.01]
+//   rm_train view     --scene scene.json [--out .] [--size 800x800] [--radius-offset 0] [--device 0]
+//                     [--pos 0,0,-2.5 --yaw 90 --pitch 0 | --orbit N [--orbit-radius 2.5 --orbit-height 0]]
+//     the reference viewer's frames (src/bin/viewer.rs), headless: out/frame_<i>.png, one per pose
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,13 +39,15 @@ namespace {
 
 int usage() {
   std::fprintf(stderr,
-               "usage: rm_train train|generate|preview [options]\n"
+               "usage: rm_train train|generate|preview|view [options]\n"
                "  train    --cameras F --out D --stages N --steps N --batch N --size WxH --march-steps N\n"
                "           --seed N --log-every N --no-previews --device N --ranks N\n"
                "           --split-scale F --split-move F --split-all --max-spheres N --color-f16\n"
                "           --rank R --world N --comm-file F --run-id S --comm-timeout SEC\n"
                "  generate --out D --prefix P --size WxH --device N\n"
-               "  preview  --scene F --png F --size WxH --eye x,y,z --target x,y,z --fov F --radius-offset F\n");
+               "  preview  --scene F --png F --size WxH --eye x,y,z --target x,y,z --fov F --radius-offset F\n"
+               "  view     --scene F --out D --size WxH [--pos x,y,z --yaw DEG --pitch DEG | --orbit N\n"
+               "           --orbit-radius R --orbit-height Y] --radius-offset F --device N\n");
   return 2;
 }
 
@@ -259,6 +265,53 @@ int main(int argc, char** argv) {
     }
     if (!scene || !png) return usage();
     return report(rmh_preview(scene, png, w, h, eye, tgt, fov, roff, dev), "preview");
+  }
+  if (cmd == "view") {
+    const char* scene = nullptr;
+    const char* out = ".";
+    int32_t w = 800, h = 800, dev = 0, orbit = 0;  // viewer.rs:125 opens an 800x800 window
+    float pos[3] = {0.0f, 0.0f, -2.5f}, yaw = 90.0f, pitch = 0.0f, roff = 0.0f;  // viewer.rs:297-300
+    float orbit_radius = 2.5f, orbit_height = 0.0f;
+    for (int i = 2; i < argc; ++i) {
+      const std::string a = argv[i];
+      if (!need(i)) return usage();
+      if (a == "--scene") scene = argv[++i];
+      else if (a == "--out") out = argv[++i];
+      else if (a == "--size") {
+        if (!parse_size(argv[++i], w, h)) return usage();
+      } else if (a == "--pos") {
+        if (!parse_vec3(argv[++i], pos)) return usage();
+      } else if (a == "--yaw") yaw = (float)std::atof(argv[++i]);
+      else if (a == "--pitch") pitch = (float)std::atof(argv[++i]);
+      else if (a == "--orbit") orbit = std::atoi(argv[++i]);
+      else if (a == "--orbit-radius") orbit_radius = (float)std::atof(argv[++i]);
+      else if (a == "--orbit-height") orbit_height = (float)std::atof(argv[++i]);
+      else if (a == "--radius-offset") roff = (float)std::atof(argv[++i]);
+      else if (a == "--device") dev = std::atoi(argv[++i]);
+      else return usage();
+    }
+    if (!scene || orbit < 0) return usage();
+    const double deg = 3.14159265358979323846 / 180.0;
+    std::vector<rmh_view_pose> cams;
+    if (orbit == 0) {
+      cams.resize(1);
+      rmh_view_camera(pos, (float)(yaw * deg), (float)(pitch * deg), &cams[0]);
+    } else {
+      // N poses on a circle about the y axis, each looking at the origin: pose i stands at angle
+      // 2 pi i / N from the viewer's start direction (0, y, -r)
+      cams.resize(orbit);
+      const double r = orbit_radius, y = orbit_height;
+      for (int i = 0; i < orbit; ++i) {
+        const double ang = -0.5 * 3.14159265358979323846 + 2.0 * 3.14159265358979323846 * i / orbit;
+        const float p[3] = {(float)(r * std::cos(ang)), (float)y, (float)(r * std::sin(ang))};
+        // looking at the origin: forward = -p / |p|
+        const double yw = std::atan2(-(double)p[2], -(double)p[0]);
+        const double pt = std::atan2(-(double)p[1], std::sqrt((double)p[0] * p[0] + (double)p[2] * p[2]));
+        rmh_view_camera(p, (float)yw, (float)pt, &cams[i]);
+      }
+    }
+    const std::string pattern = std::string(out) + "/frame_%d.png";
+    return report(rmh_view(scene, pattern.c_str(), w, h, cams.data(), (int32_t)cams.size(), roff, dev), "view");
   }
   return usage();
 }

@@ -300,6 +300,10 @@ int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres) {
   if ((rc = ctx->opt_arrival.ensure(ctx, 128, "optimizer counter", true)) != RM_OK) return rc;
   if ((rc = ctx->opt_pre.ensure(ctx, sizeof(float) * (4 * kOptPreStride + 2), "optimizer hand-off")) != RM_OK) return rc;
   if ((rc = ctx->rg_ws.ensure(ctx, rg_need(rays), "ray-gradient workspace")) != RM_OK) return rc;
+  {  // the sphere records: all the scratch rm_view takes
+    const int np = pad_spheres(max_spheres) / 2;
+    if ((rc = ctx->rec.ensure(ctx, rec_bytes(np, (np + 255) / 256), "record buffer")) != RM_OK) return rc;
+  }
   return ctx->ws.ensure(ctx, ws_need(rays, max_spheres), "workspace");
 }
 
@@ -655,6 +659,38 @@ int rm_render_diff_backward_cameras(rm_context* ctx, const rm_camera* cams, int3
   c.grad_cams = grad_cams;
   c.accumulate = accumulate;
   return run_raygrad(ctx, c);
+}
+
+void rm_view_params_default(rm_view_params* p) {
+  if (!p) return;
+  p->max_steps = 100;          // shader.wgsl MAX_STEPS
+  p->smooth_k = 32.0f;         // viewer.rs smooth_k
+  p->hit_eps = 1e-3f;          // shader.wgsl: d < 0.001
+  p->t_max = 20.0f;            // shader.wgsl: t > 20.0
+  p->normal_eps = 1e-3f;       // shader.wgsl calc_normal
+  p->color_sharpness = 10.0f;  // shader.wgsl: exp(-10 d)
+  p->focal = 1.5f;             // shader.wgsl: 1.5 * ww
+  p->flags = 0;
+}
+
+int rm_view(rm_context* ctx, const rm_view_camera* cams, int32_t num_frames, int32_t width, int32_t height,
+            const rm_scene* scene, const rm_view_params* params, float* out_rgb, uint8_t* out_rgba8,
+            float* out_depth) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  rm_view_params vp;
+  rm_view_params_default(&vp);
+  if (params) vp = *params;
+  if (!cams) return fail(ctx, RM_ERR_INVALID_ARG, "cams is NULL");
+  if (num_frames < 1 || num_frames > RM_MAX_VIEWS_PER_CALL)
+    return fail(ctx, RM_ERR_INVALID_ARG, "num_frames %d out of [1, %d]", num_frames, RM_MAX_VIEWS_PER_CALL);
+  if (width < 1 || height < 1 || (long long)width * height > (1LL << 28))
+    return fail(ctx, RM_ERR_INVALID_ARG, "bad frame size %dx%d", width, height);
+  if (vp.max_steps < 1) return fail(ctx, RM_ERR_INVALID_ARG, "max_steps %d < 1", vp.max_steps);
+  if (!out_rgb && !out_rgba8 && !out_depth) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
+  if ((reinterpret_cast<uintptr_t>(out_rgba8) & 3) != 0) return fail(ctx, RM_ERR_INVALID_ARG, "out_rgba8 is not 4-byte aligned");
+  if (!std::isfinite(vp.focal) || !std::isfinite(vp.hit_eps) || !std::isfinite(vp.color_sharpness))
+    return fail(ctx, RM_ERR_INVALID_ARG, "focal, hit_eps and color_sharpness must be finite");
+  return run_view(ctx, cams, num_frames, width, height, scene, vp, out_rgb, out_rgba8, out_depth);
 }
 
 }  // extern "C"

@@ -2730,6 +2730,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
 #include "rm_reduce.h"
 #include "rm_small.h"
 #include "rm_raygrad.h"
+#include "rm_view.h"
 
 // rm_debug_stall: one wave that holds its stream until the host sets *flag (a system-scope load
 // of host-mapped memory, polled with s_sleep) or max_ticks of the 100 MHz real-time counter have

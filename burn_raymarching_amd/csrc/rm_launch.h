@@ -1,7 +1,7 @@
 // rm_launch.h -- launch orchestration behind the C ABI: what a call is (Geometry, Call,
 // RayGradCall), its checks and its KArgs, and the launch sequences of the general kernel (run),
-// the small-scene kernel (run_small), the ray-gradient kernel (run_raygrad) and the gradient
-// reduction. Host code only; included by rm_kernels.hip after rm_context.h.
+// the small-scene kernel (run_small), the ray-gradient kernel (run_raygrad), the viewer's frame
+// render (run_view) and the gradient reduction. Host code only; included by rm_kernels.hip after rm_context.h.
 #pragma once
 
 namespace {
@@ -987,6 +987,88 @@ int run_raygrad(rm_context* ctx, const RayGradCall& c) {
                           a, r);
     RM_HIP(ctx, hipGetLastError());
     done += nr;
+  }
+  return RM_OK;
+}
+
+// ---- the viewer's frame render (rm_view.h) ---------------------------------------------------
+
+// viewer.rs:65-86 / shader.wgsl:108-110 in f32: ro and the basis ww, uu = ww x up, vv = uu x ww
+void make_view_cam(const rm_view_camera& c, ViewCam& b) {
+  auto normalize = [](const float v[3], float out[3]) {
+    const float len = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    for (int k = 0; k < 3; ++k) out[k] = v[k] / len;
+  };
+  auto cross = [](const float a[3], const float bb[3], float out[3]) {
+    out[0] = a[1] * bb[2] - a[2] * bb[1];
+    out[1] = a[2] * bb[0] - a[0] * bb[2];
+    out[2] = a[0] * bb[1] - a[1] * bb[0];
+  };
+  float x[3];
+  normalize(c.forward, b.ww);
+  cross(b.ww, c.up, x);
+  normalize(x, b.uu);
+  cross(b.uu, b.ww, x);
+  normalize(x, b.vv);
+  for (int k = 0; k < 3; ++k) b.pos[k] = c.pos[k];
+}
+
+int run_view(rm_context* ctx, const rm_view_camera* cams, int frames, int W, int H, const rm_scene* scene,
+             const rm_view_params& vp, float* out_rgb, uint8_t* out_rgba8, float* out_depth) {
+  ctx->opt_prepared = false;
+  int rc;
+  // the record kernel takes the scene and k through a march description
+  rm_march m;
+  rm_march_default(&m);
+  m.steps = vp.max_steps;
+  m.smooth_k = vp.smooth_k;
+  m.normal_eps = vp.normal_eps;
+  m.color_sharpness = vp.color_sharpness;
+  m.mask_sharpness = 0.0f;
+  m.flags = vp.flags & RM_MARCH_COLOR_F16;
+  Geometry g;
+  g.scene = scene;
+  g.march = &m;
+  if ((rc = check_scene(ctx, scene, true)) != RM_OK) return rc;
+  if ((rc = check_march(ctx, &m)) != RM_OK) return rc;
+  KArgs a;
+  std::memset(&a, 0, sizeof a);
+  fill_scene_args(g, a);
+  if ((rc = prepare_records(ctx, a, false)) != RM_OK) return rc;
+
+  ViewArgs v;
+  std::memset(&v, 0, sizeof v);
+  v.rec_buf = a.rec_buf;
+  v.Mpad = a.Mpad;
+  v.width = W;
+  v.height = H;
+  v.tiles_x = (W + 15) / 16;
+  v.max_steps = vp.max_steps;
+  v.kappa = vp.smooth_k * kLog2e;
+  v.hit_eps = vp.hit_eps;
+  v.t_max = vp.t_max;
+  v.normal_eps = vp.normal_eps;
+  v.c10l = vp.color_sharpness * kLog2e;
+  v.focal = vp.focal;
+  v.count_iters = (vp.flags & RM_VIEW_COUNT_ITERATIONS) != 0;
+  // the exact skips need every step to advance the ray (d >= hit_eps > 0), see rm_view.h
+  // (the bounding radius R is in the record header on the device: the kernel adds it)
+  const bool exits = (vp.flags & RM_MARCH_NO_EARLY_EXIT) == 0 && !v.count_iters && vp.hit_eps > 0.0f;
+  v.skip_add = exits ? vp.hit_eps + a.lse_slack + 1e-3f : 0.0f;
+  v.light_dir = scene->light_dir;
+  v.ambient = scene->ambient;
+  v.out_rgb = out_rgb;
+  v.out_rgba8 = out_rgba8;
+  v.out_depth = out_depth;
+  const unsigned tiles = (unsigned)v.tiles_x * (unsigned)((H + 15) / 16);
+  for (int f0 = 0; f0 < frames; f0 += kViewInline) {
+    const int nf = std::min(kViewInline, frames - f0);
+    for (int f = 0; f < nf; ++f) make_view_cam(cams[f0 + f], v.cams[f]);
+    v.frame0 = f0;
+    hipEvent_t ev0, ev1;
+    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
+    hipExtLaunchKernelGGL(rm_view_kernel, dim3(tiles, (unsigned)nf), dim3(kBlock), 0, ctx->stream, ev0, ev1, 0u, v);
+    RM_HIP(ctx, hipGetLastError());
   }
   return RM_OK;
 }

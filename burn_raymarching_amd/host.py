@@ -67,6 +67,10 @@ class RmhTrainResult(ctypes.Structure):
                 ("seconds", ctypes.c_double), ("step_ms", ctypes.c_double)]
 
 
+class RmhViewPose(ctypes.Structure):
+    _fields_ = [("pos", ctypes.c_float * 3), ("forward", ctypes.c_float * 3), ("up", ctypes.c_float * 3)]
+
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
@@ -111,6 +115,10 @@ SIGNATURES = {
     "rmh_train_config_default": (None, [ctypes.POINTER(RmhTrainConfig)]),
     "rmh_train": (ctypes.c_int, [ctypes.POINTER(RmhTrainConfig), ctypes.POINTER(RmhTrainResult), _P, _I32]),
     "rmh_preview": (ctypes.c_int, [_S, _S, _I32, _I32, _P, _P, _F, _F, _I32]),
+    "rmh_view_camera": (None, [_P, _F, _F, ctypes.POINTER(RmhViewPose)]),
+    "rmh_view": (ctypes.c_int, [_S, _S, _I32, _I32, ctypes.POINTER(RmhViewPose), _I32, _F, _I32]),
+    "rmh_png_write_rgba": (ctypes.c_int, [_S, _P, _I32, _I32]),
+    "rmh_png_read_rgba": (ctypes.c_int, [_S, _PI32, _PI32, _PP]),
     "rmh_generate": (ctypes.c_int, [_S, _S, _I32, _I32, _I32]),
     "rmh_version": (ctypes.c_char_p, []),
 }
@@ -441,6 +449,34 @@ def preview(scene_json, png_path, width=256, height=256, eye=(0.0, 0.0, -2.5), t
     t = _f32c(target, (3,))
     _check(lib().rmh_preview(_b(scene_json), _b(png_path), width, height, _p(e), _p(t), fov, radius_offset, device),
            "rmh_preview")
+
+
+def view_camera(pos, yaw, pitch) -> RmhViewPose:
+    """rmh_view_camera: the viewer's pose (viewer.rs:65-86) from position, yaw and pitch (radians)."""
+    out = RmhViewPose()
+    lib().rmh_view_camera(_p(_f32c(pos, (3,))), yaw, pitch, ctypes.byref(out))
+    return out
+
+
+def view(scene_json, out_pattern, width, height, poses, radius_offset=0.0, device=0) -> None:
+    """rmh_view: the reference viewer's frames of a scene.json, one RGBA PNG per pose."""
+    poses = list(poses)
+    arr = (RmhViewPose * max(len(poses), 1))(*poses)
+    _check(lib().rmh_view(_b(scene_json), _b(out_pattern), width, height, arr, len(poses), radius_offset, device),
+           "rmh_view")
+
+
+def png_read_rgba(path) -> np.ndarray:
+    w, h, p = _I32(), _I32(), _P()
+    _check(lib().rmh_png_read_rgba(_b(path), ctypes.byref(w), ctypes.byref(h), ctypes.byref(p)), "rmh_png_read_rgba")
+    return _take(p, w.value * h.value * 4, np.uint8).reshape(h.value, w.value, 4)
+
+
+def png_write_rgba(path, rgba: np.ndarray) -> None:
+    rgba = np.ascontiguousarray(rgba, dtype=np.uint8)
+    if rgba.ndim != 3 or rgba.shape[2] != 4:
+        raise ValueError("rgba must be [h, w, 4]")
+    _check(lib().rmh_png_write_rgba(_b(path), _p(rgba), rgba.shape[1], rgba.shape[0]), "rmh_png_write_rgba")
 
 
 def generate(out_dir, prefix="data/", width=256, height=256, device=0) -> None:

@@ -55,6 +55,18 @@ class RmCamera(ctypes.Structure):
     _fields_ = [("eye", _F * 3), ("target", _F * 3), ("fov_deg", _F)]
 
 
+class RmViewCamera(ctypes.Structure):
+    _fields_ = [("pos", _F * 3), ("forward", _F * 3), ("up", _F * 3)]
+
+
+class RmViewParams(ctypes.Structure):
+    _fields_ = [("max_steps", _I32), ("smooth_k", _F), ("hit_eps", _F), ("t_max", _F), ("normal_eps", _F),
+                ("color_sharpness", _F), ("focal", _F), ("flags", _I32)]
+
+
+RM_VIEW_COUNT_ITERATIONS = 65536
+
+
 class RmGrads(ctypes.Structure):
     _fields_ = [("centers", _P), ("colors", _P), ("radius", _P), ("light_dir", _P), ("ambient", _P)]
 
@@ -89,6 +101,9 @@ SIGNATURES = {
                                             ctypes.POINTER(RmGrads), _P, _P, _I32]),
     "rm_render": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _P, _I32, _P]),
     "rm_render_camera": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
+    "rm_view_params_default": (None, [ctypes.POINTER(RmViewParams)]),
+    "rm_view": (ctypes.c_int, [_P, ctypes.POINTER(RmViewCamera), _I32, _I32, _I32, ctypes.POINTER(RmScene),
+                               ctypes.POINTER(RmViewParams), _P, _P, _P]),
     "rm_gather_rays": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P]),
     "rm_sample_batch": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, ctypes.c_uint64, ctypes.c_uint64,
                                        ctypes.c_uint64, _P, _P, _P, _P]),
@@ -254,6 +269,30 @@ def march_params(steps=40, smooth_k=32.0, normal_eps=1e-4, color_sharpness=10.0,
         flags |= RM_MARCH_FORCE_MAX_SHIFT
     return RmMarch(int(steps), float(smooth_k), float(normal_eps), float(color_sharpness), float(mask_sharpness),
                    flags)
+
+
+def view_params(**kw) -> RmViewParams:
+    """rm_view_params with the reference viewer's values (rm_view_params_default: 100 iterations,
+    k = 32, hit at 1e-3, t_max 20, normal_eps 1e-3, colour sharpness 10, focal 1.5); keyword
+    arguments override fields."""
+    p = RmViewParams()
+    lib().rm_view_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        if k not in dict(RmViewParams._fields_):
+            raise TypeError(f"rm_view_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def view_cameras(cams) -> ctypes.Array:
+    """cams: iterable of (pos[3], forward[3], up[3]) viewer poses."""
+    cams = list(cams)
+    arr = (RmViewCamera * max(len(cams), 1))()
+    for i, (pos, fwd, up) in enumerate(cams):
+        arr[i].pos[:] = [float(x) for x in pos]
+        arr[i].forward[:] = [float(x) for x in fwd]
+        arr[i].up[:] = [float(x) for x in up]
+    return arr
 
 
 def cameras(cams) -> ctypes.Array:

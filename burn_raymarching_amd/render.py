@@ -11,7 +11,9 @@ Names and argument meaning follow the reference:
     ``render_diff_backward_rays`` / ``render_diff_backward_cameras`` -- the ray / pose gradients;
   * ``train_step(...)`` -- forward + compute_loss reconstruction seed + backward fused;
   * ``create_camera_rays(width, height, eye, target, fov_deg)`` -- host ray
-    generation (camera.rs:30-90, a host loop in the reference too).
+    generation (camera.rs:30-90, a host loop in the reference too);
+  * ``view(cams, width, height, scene)`` / ``view_camera(pos, yaw, pitch)`` -- the reference
+    viewer's frames (viewer.rs + shader.wgsl), headless: rm_view, not differentiable.
 
 Tensors are torch CUDA (HIP) tensors, fp32, ``[N, 3]``; torch provides device memory
 and the stream only. Shapes are checked on the host before any launch.
@@ -474,3 +476,51 @@ def render_camera(cams, width, height, centers, colors, radius):
     ctx.check(ctx._lib.rm_render_camera(ctx.handle, native.cameras(cams), len(cams), width, height, _ptr(centers),
                                         _ptr(colors), _ptr(radius), m, _ptr(out)), "rm_render_camera")
     return out
+
+
+# ---- the reference viewer, headless (src/bin/viewer.rs + shader.wgsl; rm_view) -----------------
+VIEW_START = ((0.0, 0.0, -2.5), math.pi / 2.0, 0.0)  # the viewer's first pose: pos, yaw, pitch
+
+
+def view_camera(pos, yaw, pitch):
+    """The viewer's camera (viewer.rs:65-86) as (pos, forward, up): forward = (cos yaw cos pitch,
+    sin pitch, sin yaw cos pitch) normalised, right = normalize(forward x Y), up = normalize(right x
+    forward); angles in radians. ``view_camera(*VIEW_START)`` is where the viewer starts."""
+    f = np.array([math.cos(yaw) * math.cos(pitch), math.sin(pitch), math.sin(yaw) * math.cos(pitch)], np.float64)
+    f /= np.linalg.norm(f)
+    r = np.cross(f, np.array([0.0, 1.0, 0.0]))
+    r /= np.linalg.norm(r)
+    u = np.cross(r, f)
+    u /= np.linalg.norm(u)
+    return (tuple(float(np.float32(x)) for x in pos), tuple(float(np.float32(x)) for x in f),
+            tuple(float(np.float32(x)) for x in u))
+
+
+def view(cams, width, height, scene: Scene, *, params=None, rgba8=False, depth=False):
+    """The reference viewer's frames of `scene` from the poses `cams` ((pos, forward, up) each, see
+    view_camera): sphere trace with a per-ray hit exit, four-tap tetrahedral normal, normalised
+    exp(-10 d) colour, no mask (shader.wgsl:43-128) -- not the training render. `scene` is drawn as
+    given (the viewer draws scene.json's radii without the training activation's +0.01). Returns
+    the linear RGB frames [F, H, W, 3] (float32), then, if asked for, the display-encoded RGBA8
+    frames [F, H, W, 4] (uint8: piecewise sRGB, alpha 255) and the hit depth [F, H, W] (+inf for a
+    miss). `params`: native.view_params(...). No autograd: the viewer is not differentiable."""
+    cams = list(cams)
+    f = len(cams)
+    if f == 0:
+        raise ValueError("at least one camera is required")
+    dev = scene.centers.device
+    p = native.RmViewParams.from_buffer_copy(params) if params is not None else native.view_params()
+    p.flags = (p.flags & ~native.RM_MARCH_COLOR_F16) | scene.march_flags
+    rgb = torch.empty((f, height, width, 3), device=dev)
+    px = torch.empty((f, height, width, 4), device=dev, dtype=torch.uint8) if rgba8 else None
+    dp = torch.empty((f, height, width), device=dev) if depth else None
+    ctx = context(dev)
+    for i in range(0, f, native.RM_MAX_VIEWS_PER_CALL):
+        chunk = cams[i:i + native.RM_MAX_VIEWS_PER_CALL]
+        j = i + len(chunk)
+        ctx.check(ctx._lib.rm_view(ctx.handle, native.view_cameras(chunk), len(chunk), width, height,
+                                   ctypes.byref(scene.c_struct()), ctypes.byref(p), _ptr(rgb[i:j]),
+                                   _ptr(px[i:j]) if px is not None else None,
+                                   _ptr(dp[i:j]) if dp is not None else None), "rm_view")
+    out = (rgb,) + ((px,) if rgba8 else ()) + ((dp,) if depth else ())
+    return out[0] if len(out) == 1 else out

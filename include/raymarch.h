@@ -241,6 +241,56 @@ int rm_render_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, 
                      const float* centers, const float* colors, const float* radius, int32_t num_spheres,
                      float* out);
 
+/* ---- the reference viewer, headless: src/bin/viewer.rs + src/bin/shader.wgsl ---------------- */
+/* How a user looks at the scene.json that training wrote, as frames instead of a window. The
+ * viewer's math is not the training render's: a sphere trace with a per-ray exit at a hit
+ * threshold (t = 0; up to max_steps times: d = D(pos + t rd); d < hit_eps is a hit, else t > t_max
+ * is a miss, else t += d), the four-tap tetrahedral normal at normal_eps, the normalised
+ * exp(-color_sharpness d) colour with its absolute 1e-5, Lambert + ambient, and no silhouette mask:
+ * a miss is exactly 0. Pixel (i, j) of a frame, row 0 at the top, looks along
+ * normalize(ux uu + uy vv + focal ww) with ux = (2 (i + .5) / W - 1) W / H, uy = 1 - 2 (j + .5) / H,
+ * ww = normalize(forward), uu = normalize(ww x up), vv = normalize(uu x ww) (shader.wgsl:104-112).
+ * Two stated differences from the reference: the soft-min is a shifted
+ * log-sum-exp, so it keeps rendering where the shader's unshifted fp32 fold underflows to log(0)
+ * (every sphere farther than about 2.7 units) and the reference goes black; and a tap sum of exactly
+ * zero gives a zero diffuse term, not NaN. Not differentiable. */
+typedef struct rm_view_camera {
+  float pos[3];
+  float forward[3];
+  float up[3];
+} rm_view_camera;
+typedef struct rm_view_params {
+  int32_t max_steps;      /* trace iterations, shader.wgsl MAX_STEPS (100)              */
+  float smooth_k;         /* soft-min sharpness (32)                                    */
+  float hit_eps;          /* hit threshold on D (1e-3)                                  */
+  float t_max;            /* a ray past this t is a miss (20)                           */
+  float normal_eps;       /* tetrahedral tap distance (1e-3)                            */
+  float color_sharpness;  /* exp(-c d) colour weights (10)                              */
+  float focal;            /* image plane distance (1.5)                                 */
+  int32_t flags;          /* RM_MARCH_COLOR_F16, RM_MARCH_NO_EARLY_EXIT, RM_VIEW_* bits  */
+} rm_view_params;
+/* Diagnostics: out_depth receives the number of soft-min evaluations the ray's trace made (as a
+ * float, 0 for no ray) instead of its depth; the exact skips are off, so it is the count of the
+ * trace as specified. */
+#define RM_VIEW_COUNT_ITERATIONS 65536
+void rm_view_params_default(rm_view_params* params);   /* 100, 32, 1e-3, 20, 1e-3, 10, 1.5, 0 */
+/* Renders num_frames (1 .. RM_MAX_VIEWS_PER_CALL) frames of width x height from the poses cams
+ * (HOST memory, like rm_camera). scene is used as given: scene.json stores the radii without the
+ * +0.01 of the training activation and the reference viewer draws them so; whether to add it is
+ * the caller's business. Outputs (device pointers, any may be NULL but not all three):
+ *   out_rgb   [F,H,W,3] linear float RGB;
+ *   out_rgba8 [F,H,W,4] (4-byte aligned) the bytes the viewer's sRGB surface shows: the piecewise
+ *             sRGB encode (12.92 c below 0.0031308, else 1.055 c^(1/2.4) - 0.055) rounded to
+ *             nearest, alpha 255 -- not the gamma-1/2.2 truncation of the training PNGs (util.rs);
+ *   out_depth [F,H,W] t at the hit, +inf for a miss.
+ * Rays that provably cannot hit (their line stays outside the scene's bounding sphere grown by
+ * hit_eps + ln(M)/k and a rounding margin, or they recede beyond it) end as misses without further
+ * marching; RM_MARCH_NO_EARLY_EXIT in flags turns that off: the same bits either way. params NULL =
+ * the defaults. Two identical calls give identical bits. */
+int rm_view(rm_context* ctx, const rm_view_camera* cams, int32_t num_frames, int32_t width, int32_t height,
+            const rm_scene* scene, const rm_view_params* params, float* out_rgb, uint8_t* out_rgba8,
+            float* out_depth);
+
 /* ---- batch gather: SceneDataset::sample_batch, dataset.rs:75-79 ---------------- */
 /* out_*[i] = src[indices[i]] for the ray origin, direction and target arrays ([num_src,3]
  * each; any output may be NULL to skip it). indices is a device int32 [num_rays]; an index

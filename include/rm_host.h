@@ -237,6 +237,30 @@ int rmh_train(const rmh_train_config* cfg, rmh_train_result* result, float* raw_
 int rmh_preview(const char* scene_json, const char* png_path, int32_t width, int32_t height, const float eye[3],
                 const float target[3], float fov_deg, float radius_offset, int32_t device);
 
+/* ---- viewer.rs + shader.wgsl: the viewer's frames of a scene.json, headless -------------- */
+/* A viewer pose: the layout of rm_view_camera (raymarch.h). */
+typedef struct rmh_view_pose {
+  float pos[3];
+  float forward[3];
+  float up[3];
+} rmh_view_pose;
+/* The viewer's camera (viewer.rs:65-86) from its position, yaw and pitch (radians):
+ * forward = (cos yaw cos pitch, sin pitch, sin yaw cos pitch) normalised, right =
+ * normalize(forward x Y), up = normalize(right x forward). The viewer starts at pos (0, 0, -2.5),
+ * yaw pi/2, pitch 0. */
+void rmh_view_camera(const float pos[3], float yaw, float pitch, rmh_view_pose* out);
+/* Loads scene_json as viewer.rs does -- the stored radii, radius_offset (0 by default) added --
+ * renders the `count` poses with rm_view and writes one RGBA PNG per frame from its RGBA8 output
+ * (the bytes the viewer's sRGB surface shows). out_pattern names the files: a "%d" in it takes the
+ * frame index; without one, a single frame goes to out_pattern itself and several frames get
+ * "_<index>" before the extension. */
+int rmh_view(const char* scene_json, const char* out_pattern, int32_t width, int32_t height,
+             const rmh_view_pose* cams, int32_t count, float radius_offset, int32_t device);
+/* RGBA8 [h][w][4] -> PNG (colour type 6); creates missing parent directories. */
+int rmh_png_write_rgba(const char* path, const uint8_t* rgba, int32_t width, int32_t height);
+/* 8-bit PNG -> RGBA8 [h][w][4] (alpha 255 where the file has none). */
+int rmh_png_read_rgba(const char* path, int32_t* width, int32_t* height, uint8_t** rgba);
+
 /* ---- generate.rs:20-112: target images + cameras.json ---------------------------------- */
 /* Renders the three-sphere scene from the 10 generate.rs cameras with rm_render_camera and
  * writes out_dir/target_i.png plus out_dir/cameras.json ("file" entries are
