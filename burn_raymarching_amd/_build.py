@@ -2,7 +2,7 @@
 
   burn_raymarching_amd/lib/libraymarch_hip.so  <- csrc/rm_kernels.hip   (the product: C ABI of include/raymarch.h;
                                                   one translation unit: the kernels in rm_kernels.hip and
-                                                  rm_{device,reduce,small,raygrad,view}.h, the host side in
+                                                  rm_{device,ray,reduce,small,raygrad,view}.h, the host side in
                                                   rm_{context,launch,api}.h)
   burn_raymarching_amd/lib/librm_host.so        <- csrc/host/{io,data,driver,comm}.cpp (C ABI of include/rm_host.h; RCCL)
   burn_raymarching_amd/lib/rm_train             <- csrc/host/main.cpp    (CLI: train / generate / preview / view)
@@ -46,6 +46,7 @@ def _stale(target: str, sources) -> bool:
 KERNEL_SOURCES = [os.path.join(CSRC, "rm_kernels.hip"), os.path.join(CSRC, "rm_device.h"),
                   os.path.join(CSRC, "rm_reduce.h"), os.path.join(CSRC, "rm_small.h"),
                   os.path.join(CSRC, "rm_raygrad.h"), os.path.join(CSRC, "rm_view.h"),
+                  os.path.join(CSRC, "rm_ray.h"),
                   os.path.join(CSRC, "rm_context.h"),
                   os.path.join(CSRC, "rm_launch.h"), os.path.join(CSRC, "rm_api.h"),
                   os.path.join(ROOT, "include", "raymarch.h")]

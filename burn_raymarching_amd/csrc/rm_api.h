@@ -178,16 +178,16 @@ int rm_timing_collect(rm_context* ctx, double* total_ms, int64_t* launches, int3
 
 int rm_debug_order_counts(rm_context* ctx, int32_t* counts, int32_t capacity, int32_t* classes, int32_t* next_set) {
   if (!ctx) return RM_ERR_INVALID_ARG;
-  constexpr int kCls = RM_ORDER_CLASSES;
+  constexpr int kCls = kOrderClasses;
   if (classes) *classes = kCls;
   if (counts && capacity < 3 * kCls) return fail(ctx, RM_ERR_INVALID_ARG, "counts needs %d entries", 3 * kCls);
   RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  std::vector<int> host(4 * RM_ORDER_CNT_STRIDE, 0);  // the sets' counts and the device turn word
+  std::vector<int> host(4 * kOrderCntStride, 0);  // the sets' counts and the device turn word
   if (ctx->ocnt) RM_HIP(ctx, hipMemcpy(host.data(), ctx->ocnt.p, sizeof(int) * host.size(), hipMemcpyDeviceToHost));
-  if (next_set) *next_set = host[3 * RM_ORDER_CNT_STRIDE];
+  if (next_set) *next_set = host[3 * kOrderCntStride];
   if (counts)
     for (int st = 0; st < 3; ++st)
-      for (int c = 0; c < kCls; ++c) counts[st * kCls + c] = host[st * RM_ORDER_CNT_STRIDE + c * RM_ORDER_CLS_STRIDE];
+      for (int c = 0; c < kCls; ++c) counts[st * kCls + c] = host[st * kOrderCntStride + c * kOrderClsStride];
   return RM_OK;
 }
 

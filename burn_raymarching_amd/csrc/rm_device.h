@@ -11,14 +11,8 @@
 
 namespace rm {
 
-#ifndef RM_BLOCK
-#define RM_BLOCK 256
-#endif
-constexpr int kBlock = RM_BLOCK;         // threads per block (256 = 4 waves)
-#ifndef RM_MIN_WAVES
-#define RM_MIN_WAVES 4
-#endif
-constexpr int kMinWavesPerSimd = RM_MIN_WAVES;  // register budget: 4 -> <= 128 VGPRs
+constexpr int kBlock = 256;              // threads per block (256 = 4 waves)
+constexpr int kMinWavesPerSimd = 4;      // register budget: 4 -> <= 128 VGPRs
 constexpr int kWaves = kBlock / 64;
 constexpr int kSphereAlign = 32;         // M is padded to a multiple of this
 constexpr float kLog2e = 1.4426950408889634f;
@@ -31,10 +25,7 @@ constexpr float kPadCenter = 1e15f;      // padding sphere center x: distance ~1
 constexpr float kTMax = 1e15f;
 // A live wave's post-march forward and backward sweeps in march-step units (the cost-ordered
 // dispatch's estimate; tools/bench_parts.py: ~8-10).
-#ifndef RM_POST_COST
-#define RM_POST_COST 10
-#endif
-constexpr int kPostCost = RM_POST_COST;
+constexpr int kPostCost = 10;
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 

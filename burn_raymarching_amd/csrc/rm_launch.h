@@ -10,7 +10,7 @@ using namespace rm;
 
 int pad_spheres(int M) { return (M + kSphereAlign - 1) / kSphereAlign * kSphereAlign; }
 // column blocks of the reduction at the largest scene (RM_MAX_SPHERES): its arrival counters
-constexpr int kRedArrivals = (RM_MAX_SPHERES * 8 + 8 + 255) / 256 * RM_RED_ARR_STRIDE;
+constexpr int kRedArrivals = (RM_MAX_SPHERES * 8 + 8 + 255) / 256 * kRedArrStride;
 
 // Ray blocks per per-ray launch: kMaxBlocksPerLaunch, or less with the environment variable
 // RM_MAX_BLOCKS_PER_LAUNCH (tests use it to exercise the sub-launch split at small sizes).
@@ -588,27 +588,27 @@ void launch_escape(bool cam, dim3 grid, hipStream_t st, const KArgs& a, int* fla
     hipLaunchKernelGGL((rm_escape_kernel<MODE, false>), grid, dim3(kBlock), 0, st, a, flags);
 }
 
+// Launches the per-ray kernel; false for a combination that is not built: the renderer.rs mode
+// never takes the split march (march_policy).
 template <int MODE>
-void launch_cont(bool cam, dim3 grid, size_t lds, hipStream_t st, const KArgs& a, hipEvent_t ev0, hipEvent_t ev1) {
-  const dim3 blk(64 * kSplitWaves);
-  if (cam) hipExtLaunchKernelGGL((rm_cont_kernel<MODE, true>), grid, blk, (uint32_t)lds, st, ev0, ev1, 0u, a);
-  else hipExtLaunchKernelGGL((rm_cont_kernel<MODE, false>), grid, blk, (uint32_t)lds, st, ev0, ev1, 0u, a);
-}
-
-template <int MODE>
-void launch_ray(bool cam, bool split, dim3 grid, size_t lds, hipStream_t st, const KArgs& a, hipEvent_t ev0,
+bool launch_ray(bool cam, bool split, dim3 grid, size_t lds, hipStream_t st, const KArgs& a, hipEvent_t ev0,
                 hipEvent_t ev1) {
   // With timing on, the start/stop timestamps come from the kernel's own dispatch packet
   // (hipExtLaunchKernel): no extra barrier packets or cache flushes around the launch.
   const dim3 blk(split ? 64 * kSplitWaves : kBlock);
   const uint32_t sh = (uint32_t)lds;
   if (split) {
-    if (cam) hipExtLaunchKernelGGL((rm_ray_kernel<MODE, true, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
-    else hipExtLaunchKernelGGL((rm_ray_kernel<MODE, false, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
+    if constexpr (MODE == kRender) {
+      return false;
+    } else {
+      if (cam) hipExtLaunchKernelGGL((rm_ray_kernel<MODE, true, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
+      else hipExtLaunchKernelGGL((rm_ray_kernel<MODE, false, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
+    }
   } else {
     if (cam) hipExtLaunchKernelGGL((rm_ray_kernel<MODE, true, false>), grid, blk, sh, st, ev0, ev1, 0u, a);
     else hipExtLaunchKernelGGL((rm_ray_kernel<MODE, false, false>), grid, blk, sh, st, ev0, ev1, 0u, a);
   }
+  return true;
 }
 
 // The call's outputs and inputs against its mode.
@@ -728,14 +728,14 @@ int bind_cost_order(rm_context* ctx, const Call& c, const Launch& l, KArgs& a) {
   if (a.block_order != nullptr && l.nb == l.blocks_left && l.done == 0 && (c.march->flags & RM_MARCH_STATIC_ORDER) == 0) {
     key = ((unsigned long long)c.W << 48) ^ ((unsigned long long)c.H << 32) ^ ((unsigned long long)c.views << 24) ^
           ((unsigned long long)a.Mpad << 1) ^ 1ull ^ ((unsigned long long)(a.split != 0) << 2);
-    constexpr int kCls = RM_ORDER_CLASSES;
+    constexpr int kCls = kOrderClasses;
     int rc;
     if ((rc = ctx->olist.ensure(ctx, sizeof(int) * 3 * kCls * kMaxBlocksPerLaunch, "cost-order lists")) != RM_OK) return rc;
-    // the three sets' counts, then the turn word, RM_ORDER_CNT_STRIDE ints apart
-    if ((rc = ctx->ocnt.ensure(ctx, sizeof(int) * 4 * RM_ORDER_CNT_STRIDE, "cost-order counts", true)) != RM_OK) return rc;
+    // the three sets' counts, then the turn word, kOrderCntStride ints apart
+    if ((rc = ctx->ocnt.ensure(ctx, sizeof(int) * 4 * kOrderCntStride, "cost-order counts", true)) != RM_OK) return rc;
     int* olist = ctx->olist.as<int>();
     int* ocnt = ctx->ocnt.as<int>();
-    ctx->oturn = ocnt + 3 * RM_ORDER_CNT_STRIDE;
+    ctx->oturn = ocnt + 3 * kOrderCntStride;
     // three list sets in rotation: the previous launch's (read), this launch's (appended;
     // cleared by the previous launch) and the next launch's (cleared by this one); which is which
     // the kernel reads from the device turn word, advanced by this call's reduction (order_sets)
@@ -776,13 +776,13 @@ int launch_with_continuations(rm_context* ctx, const Call& c, KArgs& a, long lon
   int* rcounts[2] = {nullptr, nullptr};
   if (cont) {
     const long long rays = nb * kSplitRays;
-    // per ray 8 state rows, per group 2 words (KArgs::cont_state); the group list and its count;
-    // two ray lists of up to `rays` entries and their counts
-    const size_t need = (size_t)(8 * rays + 2 * nb) * sizeof(float) + (size_t)(nb + 8 + 16) * sizeof(int) +
+    // the rays' and groups' saved states (ContState); the group list and its count; two ray lists
+    // of up to `rays` entries and their counts
+    const size_t need = ContState::floats(rays, nb) * sizeof(float) + (size_t)(nb + 8 + 16) * sizeof(int) +
                         (size_t)(2 * rays + 16) * sizeof(int);
     if ((rc = ctx->cont_buf.ensure(ctx, need, "continuation buffer")) != RM_OK) return rc;
     float* state = ctx->cont_buf.as<float>();
-    glist = reinterpret_cast<int*>(state + 8 * rays + 2 * nb);
+    glist = reinterpret_cast<int*>(state + ContState::floats(rays, nb));
     gcount = glist + nb;
     rcounts[0] = gcount + 8;  // the three counts 32 bytes apart
     rcounts[1] = rcounts[0] + 8;
@@ -798,18 +798,20 @@ int launch_with_continuations(rm_context* ctx, const Call& c, KArgs& a, long lon
     a.ray_count_w = rcounts[0];
     RM_HIP(ctx, hipMemsetAsync(gcount, 0, (8 + 16) * sizeof(int), ctx->stream));  // the three counts
   }
-  with_mode(c.mode, [&](auto m) { launch_ray<decltype(m)::value>(c.cam, split, grid, lds, ctx->stream, a, ev0, ev1); });
-  RM_HIP(ctx, hipGetLastError());
-  if (!cont) return RM_OK;
-  // rm_cont_kernel exists for the modes with a backward only (cont implies one of them)
-  auto launch_cont_mode = [&](const KArgs& b) {
-    hipEvent_t e0, e1;
-    int rc2 = next_events(ctx, e0, e1);
-    if (rc2 != RM_OK) return rc2;
-    if (c.mode == kBwd) launch_cont<kBwd>(c.cam, grid, lds, ctx->stream, b, e0, e1);
-    else launch_cont<kTrain>(c.cam, grid, lds, ctx->stream, b, e0, e1);
+  // one per-ray launch of this call's mode and march (the continuation and resume launches below
+  // run the same kernel)
+  auto launch = [&](const KArgs& b, hipEvent_t e0, hipEvent_t e1) {
+    bool built = true;
+    with_mode(c.mode, [&](auto m) { built = launch_ray<decltype(m)::value>(c.cam, split, grid, lds, ctx->stream, b, e0, e1); });
+    if (!built) return fail(ctx, RM_ERR_UNSUPPORTED, "the split march is not built for mode %d", c.mode);
     RM_HIP(ctx, hipGetLastError());
     return (int)RM_OK;
+  };
+  if ((rc = launch(a, ev0, ev1)) != RM_OK || !cont) return rc;
+  auto launch_cont_mode = [&](const KArgs& b) {
+    hipEvent_t e0, e1;
+    const int rc2 = next_events(ctx, e0, e1);
+    return rc2 != RM_OK ? rc2 : launch(b, e0, e1);
   };
   // continuation k marches the rays of ray list k % 2 (deferring at the next cap into
   // list (k + 1) % 2, whose count is cleared first: continuation k - 1 read it), then one resume

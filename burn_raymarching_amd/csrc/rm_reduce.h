@@ -36,14 +36,9 @@ struct FinalArgs {
 };
 __device__ void fused_optimizer(const FinalArgs& f, int M);
 
-#ifndef RM_REDUCE_BATCH
-#define RM_REDUCE_BATCH 8
-#endif
-constexpr int kReduceBatch = RM_REDUCE_BATCH;  // partial rows in flight per thread
-#ifndef RM_FIN_U
-#define RM_FIN_U 16  // finalize_block: 4 * RM_FIN_U loads in flight (32 with batch 16: no gain at C2)
-#endif
-static_assert((kReduceSegs / 4) % RM_FIN_U == 0, "finalize_block rounds");
+constexpr int kReduceBatch = 8;  // partial rows in flight per thread
+constexpr int kFinU = 16;        // finalize_block: 4 * kFinU loads in flight (32 with batch 16: no gain at C2)
+static_assert((kReduceSegs / 4) % kFinU == 0, "finalize_block rounds");
 
 __device__ void finalize_block(const float* S, int nseg, int M, int Mpad, const FinalArgs& f, float* tot);
 
@@ -106,7 +101,7 @@ __global__ __launch_bounds__(256) void rm_reduce_partials(const float* __restric
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) {
-    const unsigned prev = __hip_atomic_fetch_add(arrivals + blockIdx.x * RM_RED_ARR_STRIDE, 1u, __ATOMIC_RELAXED,
+    const unsigned prev = __hip_atomic_fetch_add(arrivals + blockIdx.x * kRedArrStride, 1u, __ATOMIC_RELAXED,
                                                  __HIP_MEMORY_SCOPE_AGENT);
     last = prev == gridDim.y - 1 ? 1 : 0;
   }
@@ -118,7 +113,7 @@ __global__ __launch_bounds__(256) void rm_reduce_partials(const float* __restric
   }
   __syncthreads();
   finalize_block(S, (int)gridDim.y, M, Mpad, f, tot);
-  if (tid == 0) __hip_atomic_store(arrivals + blockIdx.x * RM_RED_ARR_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) __hip_atomic_store(arrivals + blockIdx.x * kRedArrStride, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (f.raw == nullptr) return;
   // the optimizer step on the whole gradient, by the column block that finishes last: the same
   // write-through hand-off one level up (finalize_block stored its gradient elements write-through)
@@ -157,7 +152,7 @@ __device__ void finalize_block(const float* S, int nseg, int M, int Mpad, const 
   const int col = blockIdx.x * 256 + tid;
   const int c = min(col, ncols - 1);
   // kU * 4 loads in flight per thread (the last block runs alone: registers are free)
-  constexpr int kU = RM_FIN_U;
+  constexpr int kU = kFinU;
   float a[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   for (int u0 = 0; u0 < nseg / 4; u0 += kU) {
     float v[kU][4];

@@ -29,12 +29,7 @@
 #pragma once
 
 constexpr int kSmallMaxM = 32;             // spheres handled by the small kernel
-#ifndef RM_SMALL_PAR_TOTALS
-#define RM_SMALL_PAR_TOTALS 1  // final block: column totals formed once in parallel (0: per use)
-#endif
-#ifndef RM_SMALL_FIN_BATCH
-#define RM_SMALL_FIN_BATCH 32  // record rows in flight per thread in the final block's sums
-#endif
+constexpr int kSmallFinBatch = 32;         // record rows in flight per thread in the final block's sums
 constexpr int kSmallFinalMaxBlocks = 128;  // in-kernel final reduction up to this many blocks
 
 struct SmallArgs {
@@ -202,7 +197,7 @@ __device__ __forceinline__ void small_final(const KArgs& a, const SmallArgs& sa,
   // then added in order: a fixed order for every launch of this size. The write-through loads
   // miss the local L2 (~1 us each round trip): kFinBatch rows in flight per thread, so that a
   // launch of up to kSmallFinalMaxBlocks blocks takes one or two rounds.
-  constexpr int kFinBatch = RM_SMALL_FIN_BATCH;
+  constexpr int kFinBatch = kSmallFinBatch;
   const int nb = nrows;
   // A load's address is a 32-bit byte offset from the records' base (saddr form), clamped into
   // the last record instead of branching around the load (a launch's records are
@@ -236,12 +231,11 @@ __device__ __forceinline__ void small_final(const KArgs& a, const SmallArgs& sa,
   __syncthreads();
   RM_TRACE(2, __builtin_amdgcn_s_memrealtime());
   const FinalArgs& f = sa.fin;
-  // a column's total: its chains added in order. RM_SMALL_PAR_TOTALS: every column's total formed
+  // a column's total: its chains added in order. Every column's total is formed
   // once, by all threads in parallel, behind one barrier (the same adds in the same order as
   // forming it in each lane that uses it; s_red holds chains * nneed <= kBlock + 8 floats, the
   // totals go above them)
   static_assert(2 * (kBlock + 32) + 8 <= kWaves * (kSmallMaxM * 8 + 8), "s_red holds the chains and the totals");
-#if RM_SMALL_PAR_TOTALS
   float* s_tot = s_red + kBlock + 32;
   for (int idx = tid; idx < nneed; idx += kBlock) {
     float v = s_red[idx];
@@ -250,13 +244,6 @@ __device__ __forceinline__ void small_final(const KArgs& a, const SmallArgs& sa,
   }
   __syncthreads();
   auto total = [&](int idx) { return s_tot[idx]; };
-#else
-  auto total = [&](int idx) {
-    float v = s_red[idx];
-    for (int ch = 1; ch < chains; ++ch) v += s_red[ch * nneed + idx];
-    return v;
-  };
-#endif
   // FUSED: the gradient also goes to LDS in the packed layout the optimizer reads
   [[maybe_unused]] float* s_gact = nullptr;
   if constexpr (FUSED) {
