@@ -79,8 +79,13 @@ typedef struct rm_march {
  * Ignored when t_march or debug outputs are requested. */
 #define RM_MARCH_SKIP_ESCAPED 1
 /* Camera mode: launch rays in row order instead of 16x16 pixel tiles per 256-ray block (8x8
- * per wave; the default when width and height are multiples of 16). Changes only the
- * summation order of the gradients. */
+ * per wave; the default when width and height are multiples of 16). Changes the summation order
+ * of the gradients and which rays share a wave. A march step's log-sum-exp shift (unshifted,
+ * fixed or running maximum, equal to fp32 rounding) is chosen per wave from its own rays: where
+ * the scene lets the choice differ between waves (r_max + spread beyond the admission bounds of
+ * the cheaper forms, eyes inside the scene) the image and t_march move by that rounding too
+ * (2e-6 measured); on scenes that admit one form everywhere they keep their bits. In row order
+ * camera mode gives array mode's bits on the same rays. */
 #define RM_MARCH_ROW_ORDER 2
 /* Disable the escaped-ray early exit: by default a wave stops marching once all its rays
  * recede from the scene's bounding sphere at a distance where the silhouette mask is exactly
@@ -166,6 +171,22 @@ int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres);
 
 /* ---- forward: renderer_diff.rs:6-91 --------------------------------------- */
 /* out [N,3] receives render_diff(ray_org, ray_dir, scene..., smooth_k).
+ * ray_dir (every array-mode call): taken as given, p = ray_org + ray_dir t as in the reference,
+ * and nothing is rejected. The march's shortcuts, though, are proven for unit directions, |d|^2
+ * within 1 +- 4e-6 (what normalising in fp32 gives; camera mode's rays are unit by
+ * construction): the escape bound ("every step is at least |p - c| - R' long") and the
+ * clamp-free proof ("the next point is |D| away"). Unit directions are the precondition of the
+ * bit-level guarantees below (the same bits with the early exit on and off, with t_march and
+ * without). With other directions the results still follow the reference within the suite's
+ * bounds where measured (x0.25, x0.5 / x2 alternating; x0.1 with RM_MARCH_NO_EARLY_EXIT), but
+ *   - a ray shorter than unit can be taken for escaped while its mask is not yet exactly 0: a
+ *     wave of such rays returns exact zeros where the reference has tiny values (at |d| = 0.02,
+ *     48 spheres and 32 steps the reference's image is <= 3e-8 and its sphere gradients reach
+ *     1e-5), and the exit on and off differ in the last bits of out (8.8e-17 measured at
+ *     |d| = 0.25);
+ *   - a ray longer than unit can pass the clamp-free proof at a point within 1e-3 of a sphere
+ *     centre, where the reference clamps q at 1e-6.
+ * A caller with scaled directions normalises them and scales t.
  * t_march (nullable) [N] receives the detached march distance t after `steps`
  * steps (renderer_diff.rs:20-26), which rm_render_diff_backward can reuse. For a ray that
  * provably escapes the scene -- receding from its bounding sphere so far that the silhouette
@@ -173,7 +194,15 @@ int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres);
  * of that escape bound (|p - c| - R - ln(M)/k, never longer than the soft-min step), so its
  * t_march is at most the reference's t and already past the distance where the mask is 0;
  * every other ray's t_march is the reference march to fp32 rounding. Either t gives the same
- * out and gradients. */
+ * out and gradients. "To fp32 rounding" is per step: a receding ray's next step is as long as
+ * its distance from the scene, so it doubles whatever error it carries with every step. For a
+ * ray the image sees, t_march is within 1e-3 of the reference's, relative to max(1, t). A ray
+ * that hovers at a surface for most of the march and leaves in the last few steps -- unseen, not
+ * yet proven escaped -- has an ill-conditioned t: the reference's own fp64 t moves by 3e-5 under
+ * one rounding of the inputs at such a ray, and the kernels' three log-sum-exp shift forms, equal
+ * to rounding per step, end 1.9e-4 (running maximum), 7e-4 (vector units) and 1.2e-3 (default)
+ * from the fp64 t there. For those rays the bound is 64 times that sensitivity
+ * (tests/envelope_ref.py, t_bound); out and every gradient are unaffected (the mask is 0). */
 int rm_render_diff(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
                    const rm_scene* scene, const rm_march* march, float* out, float* t_march);
 /* Camera mode: rays of `num_views` cameras at width x height generated in-kernel;
