@@ -204,7 +204,16 @@ int check_march(rm_context* ctx, const rm_march* m) {
   if (m->steps < 0 || m->steps > 100000) return fail(ctx, RM_ERR_INVALID_ARG, "steps %d out of range", m->steps);
   if (!(m->smooth_k > 0.0f) || !std::isfinite(m->smooth_k))
     return fail(ctx, RM_ERR_INVALID_ARG, "smooth_k must be finite and > 0 (got %g)", (double)m->smooth_k);
-  if (!(m->normal_eps > 0.0f)) return fail(ctx, RM_ERR_INVALID_ARG, "normal_eps must be > 0");
+  if (!(m->normal_eps > 0.0f) || !std::isfinite(m->normal_eps))
+    return fail(ctx, RM_ERR_INVALID_ARG, "normal_eps must be finite and > 0 (got %g)", (double)m->normal_eps);
+  // the colour sums are shifted by the smallest sphere distance on the premise that no exponent
+  // (-csharp (d_j - d_min)) is positive; gone_d / cull_min_d assume a mask that vanishes outward
+  if (!(m->color_sharpness >= 0.0f) || !std::isfinite(m->color_sharpness))
+    return fail(ctx, RM_ERR_INVALID_ARG, "color_sharpness must be finite and >= 0 (got %g)",
+                (double)m->color_sharpness);
+  if (!(m->mask_sharpness >= 0.0f) || !std::isfinite(m->mask_sharpness))
+    return fail(ctx, RM_ERR_INVALID_ARG, "mask_sharpness must be finite and >= 0 (got %g)",
+                (double)m->mask_sharpness);
   return RM_OK;
 }
 
@@ -226,6 +235,8 @@ int check_geometry(rm_context* ctx, const Geometry& g, bool need_light) {
   return RM_OK;
 }
 
+constexpr float kMinColorSharpness = 1e-12f;
+
 // The scene and march part of a call's KArgs.
 void fill_scene_args(const Geometry& g, KArgs& a) {
   a.centers = g.scene->centers;
@@ -243,7 +254,13 @@ void fill_scene_args(const Geometry& g, KArgs& a) {
   a.steps = g.march->steps;
   a.k = g.march->smooth_k;
   a.eps = g.march->normal_eps;
-  a.csharp = g.march->color_sharpness;
+  // color_sharpness 0 (uniform colour weights) and values next to it: the padding spheres sit at
+  // distance ~1e15 (kPadCenter) and leave the colour sums only through 2^(-c log2(e) 1e15) = 0, and
+  // the sweeps start from dmin = inf, where (dn - dmin) * 0 is NaN. A sharpness below 1e-12 is
+  // raised to it: the real spheres, a few units apart, keep weights 2^(-1e-11) = 1 exactly in fp32,
+  // the padding spheres get 2^(-1443) = 0, and the colour term of the gradients is 1e-12 x a finite
+  // sum where the exact one is 0.
+  a.csharp = std::max(g.march->color_sharpness, kMinColorSharpness);
   a.msharp = g.march->mask_sharpness;
   a.lse_slack = (float)(std::log((double)a.M) / (double)a.k * (1.0 + 1e-6)) + 1e-7f;
   a.rec = rec_floats(a.Mpad);

@@ -178,7 +178,8 @@ def render_diff_backward_rays(ray_org, ray_dir, scene: Scene, smooth_k, grad_out
 
 
 def render_diff_backward_cameras(cams, width, height, scene: Scene, smooth_k, grad_out, steps=40, *, t_march=None,
-                                 grad_cams=None, accumulate=False, flags=0):
+                                 grad_cams=None, accumulate=False, normal_eps=1e-4, color_sharpness=10.0,
+                                 mask_sharpness=15.0, flags=0):
     """dL/d(eye, target, fov_deg) per view of sum(out * grad_out): a [V,7] tensor laid out as
     rm_camera (eye 0:3, target 3:6, fov_deg 6). Any number of views (chunks of 128 per call).
 
@@ -204,7 +205,7 @@ def render_diff_backward_cameras(cams, width, height, scene: Scene, smooth_k, gr
     elif _f32(grad_cams, (v, 7), "grad_cams").data_ptr() != grad_cams.data_ptr():
         raise ValueError("grad_cams must be contiguous")
     ctx = context(dev)
-    march = native.march_params(steps, smooth_k, flags=flags)
+    march = native.march_params(steps, smooth_k, normal_eps, color_sharpness, mask_sharpness, flags=flags)
     march = scene.march_for(march)
     for i in range(0, v, native.RM_MAX_VIEWS_PER_CALL):
         chunk = cams[i:i + native.RM_MAX_VIEWS_PER_CALL]
@@ -220,9 +221,12 @@ def render_diff_backward_cameras(cams, width, height, scene: Scene, smooth_k, gr
 
 class _RenderDiffFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps):
+    def forward(ctx, ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps, normal_eps,
+                color_sharpness, mask_sharpness):
         scene = Scene(centers.detach(), colors.detach(), radius.detach(), light_dir.detach(), ambient.detach())
-        out, t = render_diff_forward(ray_org.detach(), ray_dir.detach(), scene, smooth_k, steps, return_t=True)
+        ctx.consts = {"normal_eps": normal_eps, "color_sharpness": color_sharpness, "mask_sharpness": mask_sharpness}
+        out, t = render_diff_forward(ray_org.detach(), ray_dir.detach(), scene, smooth_k, steps, return_t=True,
+                                     **ctx.consts)
         ctx.save_for_backward(ray_org, ray_dir, t)
         ctx.scene = scene
         ctx.smooth_k = smooth_k
@@ -239,31 +243,34 @@ class _RenderDiffFn(torch.autograd.Function):
         g_org = g_dir = None
         if need[0] or need[1]:
             g_org, g_dir = render_diff_backward_rays(ray_org, ray_dir, ctx.scene, ctx.smooth_k, grad_out, ctx.steps,
-                                                     t_march=t, want_org=need[0], want_dir=need[1])
+                                                     t_march=t, want_org=need[0], want_dir=need[1], **ctx.consts)
         if not any(need[2:7]):  # only the rays are differentiated: the parameter backward does not run
-            return (g_org, g_dir) + (None,) * 7
-        g = render_diff_backward(ray_org, ray_dir, ctx.scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t)
+            return (g_org, g_dir) + (None,) * 10
+        g = render_diff_backward(ray_org, ray_dir, ctx.scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t,
+                                 **ctx.consts)
         return (g_org, g_dir, g["centers"], g["colors"], g["radius"].reshape(ctx.radius_shape), g["light_dir"],
-                g["ambient"].reshape(ctx.ambient_shape), None, None)
+                g["ambient"].reshape(ctx.ambient_shape), None, None, None, None, None)
 
 
-def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps=40):
+def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps=40, *,
+                normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0):
     """renderer_diff.rs:6-91 on the GPU. Differentiable w.r.t. centers, colors, radius, light_dir,
     ambient and, when they require grad, ray_org / ray_dir (see render_diff_backward_rays: the
     reference graph's gradient -- march detached, normal detached -- not the derivative of the
     image). A caller who differentiates only the scene runs the parameter backward alone."""
     return _RenderDiffFn.apply(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, float(smooth_k),
-                               int(steps))
+                               int(steps), float(normal_eps), float(color_sharpness), float(mask_sharpness))
 
 
 class _RenderDiffCamerasFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, eye, target, fov_deg, width, height, centers, colors, radius, light_dir, ambient, smooth_k,
-                steps):
+                steps, normal_eps, color_sharpness, mask_sharpness):
         scene = Scene(centers.detach(), colors.detach(), radius.detach(), light_dir.detach(), ambient.detach())
         e, tg, f = eye.detach().cpu().tolist(), target.detach().cpu().tolist(), fov_deg.detach().cpu().tolist()
         cams = [(e[i], tg[i], f[i]) for i in range(len(f))]
-        out, t = render_diff_camera(cams, width, height, scene, smooth_k, steps, return_t=True)
+        ctx.consts = {"normal_eps": normal_eps, "color_sharpness": color_sharpness, "mask_sharpness": mask_sharpness}
+        out, t = render_diff_camera(cams, width, height, scene, smooth_k, steps, return_t=True, **ctx.consts)
         ctx.save_for_backward(t)
         ctx.cams = cams
         ctx.size = (width, height)
@@ -284,7 +291,8 @@ class _RenderDiffCamerasFn(torch.autograd.Function):
         w, h = ctx.size
         g_eye = g_tgt = g_fov = None
         if need[0] or need[1] or need[2]:
-            gc = render_diff_backward_cameras(ctx.cams, w, h, ctx.scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t)
+            gc = render_diff_backward_cameras(ctx.cams, w, h, ctx.scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t,
+                                              **ctx.consts)
             ed, et, td, tt, fd, ft, fs = ctx.cam_meta
             g_eye = gc[:, 0:3].to(device=ed, dtype=et) if need[0] else None
             g_tgt = gc[:, 3:6].to(device=td, dtype=tt) if need[1] else None
@@ -296,15 +304,16 @@ class _RenderDiffCamerasFn(torch.autograd.Function):
             for i in range(0, v, native.RM_MAX_VIEWS_PER_CALL):  # the parameter backward takes 128 views a call
                 j = min(i + native.RM_MAX_VIEWS_PER_CALL, v)
                 gi = render_diff_backward_camera(ctx.cams[i:j], w, h, ctx.scene, ctx.smooth_k,
-                                                 grad_out[i * npix:j * npix], ctx.steps, t_march=t[i * npix:j * npix])
+                                                 grad_out[i * npix:j * npix], ctx.steps, t_march=t[i * npix:j * npix],
+                                                 **ctx.consts)
                 g = gi if g is None else {k: g[k] + gi[k] for k in g}
             gs = (g["centers"], g["colors"], g["radius"].reshape(ctx.radius_shape), g["light_dir"],
                   g["ambient"].reshape(ctx.ambient_shape))
-        return (g_eye, g_tgt, g_fov, None, None) + gs + (None, None)
+        return (g_eye, g_tgt, g_fov, None, None) + gs + (None,) * 5
 
 
 def render_diff_cameras(eye, target, fov_deg, width, height, centers, colors, radius, light_dir, ambient, smooth_k,
-                        steps=40):
+                        steps=40, *, normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0):
     """render_diff over the rays of create_camera_rays (camera.rs:30-90) for V cameras, differentiable
     w.r.t. the camera tensors eye [V,3], target [V,3], fov_deg [V] and the scene: out [V*H*W, 3].
 
@@ -316,7 +325,8 @@ def render_diff_cameras(eye, target, fov_deg, width, height, centers, colors, ra
     not for eye moved alone against a fixed target, where the translation and rotation parts
     nearly cancel (one of three measured cases gave a cosine of -0.93)."""
     return _RenderDiffCamerasFn.apply(eye, target, fov_deg, int(width), int(height), centers, colors, radius,
-                                      light_dir, ambient, float(smooth_k), int(steps))
+                                      light_dir, ambient, float(smooth_k), int(steps), float(normal_eps),
+                                      float(color_sharpness), float(mask_sharpness))
 
 
 def render_diff_camera(cams, width, height, scene: Scene, smooth_k, steps=40, *, normal_eps=1e-4,
@@ -343,7 +353,8 @@ def render_diff_camera(cams, width, height, scene: Scene, smooth_k, steps=40, *,
     return (out, t) if return_t else out
 
 
-def render_diff_backward_camera(cams, width, height, scene: Scene, smooth_k, grad_out, steps=40, *, t_march=None):
+def render_diff_backward_camera(cams, width, height, scene: Scene, smooth_k, grad_out, steps=40, *, t_march=None,
+                                normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0):
     cams = list(cams)
     if len(cams) > native.RM_MAX_VIEWS_PER_CALL:
         raise ValueError("at most 16 views per backward call")
@@ -353,7 +364,7 @@ def render_diff_backward_camera(cams, width, height, scene: Scene, smooth_k, gra
         t_march = _f32(t_march, (n,), "t_march")
     g, cg = _grads_like(scene)
     ctx = context(scene.centers.device)
-    march = native.march_params(steps, smooth_k)
+    march = native.march_params(steps, smooth_k, normal_eps, color_sharpness, mask_sharpness)
     march = scene.march_for(march)
     ctx.check(ctx._lib.rm_render_diff_backward_camera(ctx.handle, native.cameras(cams), len(cams), width, height,
                                                       ctypes.byref(scene.c_struct()), ctypes.byref(march),
@@ -363,7 +374,7 @@ def render_diff_backward_camera(cams, width, height, scene: Scene, smooth_k, gra
 
 
 def train_step(ray_org, ray_dir, targets, scene: Scene, smooth_k, progress, steps=40, *, inv_count=None,
-               with_out=False):
+               with_out=False, normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0):
     """Fused forward + training.rs:17-34 seed + backward over rays. Returns (loss_sum, grads, out)."""
     n = ray_org.shape[0]
     ray_org = _f32(ray_org, (n, 3), "ray_org")
@@ -375,7 +386,7 @@ def train_step(ray_org, ray_dir, targets, scene: Scene, smooth_k, progress, step
     loss = torch.zeros((1,), device=ray_org.device)
     out = torch.empty((n, 3), device=ray_org.device) if with_out else None
     ctx = context(ray_org.device)
-    march = native.march_params(steps, smooth_k)
+    march = native.march_params(steps, smooth_k, normal_eps, color_sharpness, mask_sharpness)
     march = scene.march_for(march)
     ctx.check(ctx._lib.rm_train_step(ctx.handle, _ptr(ray_org), _ptr(ray_dir), _ptr(targets), n, float(progress),
                                      float(inv_count), ctypes.byref(scene.c_struct()), ctypes.byref(march),
@@ -384,10 +395,12 @@ def train_step(ray_org, ray_dir, targets, scene: Scene, smooth_k, progress, step
 
 
 def train_step_camera(cams, width, height, targets, scene: Scene, smooth_k, progress, steps=40, *, inv_count=None,
-                      grads_packed=None, loss=None, out=None, accumulate=False, march=None, ctx=None):
+                      grads_packed=None, loss=None, out=None, accumulate=False, march=None, ctx=None,
+                      normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0):
     """Camera-mode fused train step. If grads_packed ((7M+4) device tensor) is given the
     gradients go there in the packed layout; otherwise a dict is returned. ctx: the rm_context
-    to run on (default: the one of torch's current stream)."""
+    to run on (default: the one of torch's current stream). A given `march` carries its own three
+    constants; the keywords apply when it is built here."""
     cams = list(cams)
     if not 1 <= len(cams) <= native.RM_MAX_VIEWS_PER_CALL:
         raise ValueError(f"1..{native.RM_MAX_VIEWS_PER_CALL} views per call")
@@ -406,7 +419,7 @@ def train_step_camera(cams, width, height, targets, scene: Scene, smooth_k, prog
     if loss is None:
         loss = torch.zeros((1,), device=scene.centers.device)
     if march is None:
-        march = native.march_params(steps, smooth_k)
+        march = native.march_params(steps, smooth_k, normal_eps, color_sharpness, mask_sharpness)
     march = scene.march_for(march)
     ctx.check(ctx._lib.rm_train_step_camera(ctx.handle, native.cameras(cams), len(cams), width, height, _ptr(targets),
                                             float(progress), float(inv_count), ctypes.byref(scene.c_struct()),

@@ -59,11 +59,39 @@ typedef struct rm_scene {
   int32_t num_spheres;    /* M >= 1                                      */
 } rm_scene;
 
-/* March / shading constants. rm_march_default() fills the reference's values. */
+/* March / shading constants. rm_march_default() fills the reference's values.
+ *
+ * Accepted ranges (anything else: RM_ERR_INVALID_ARG, rm_last_error names the field):
+ *   normal_eps       finite and > 0
+ *   color_sharpness  finite and >= 0 (0: uniform colour weights). The colour sums are shifted by the
+ *                    smallest sphere distance on the premise that no exponent is positive. A value
+ *                    below 1e-12 acts as 1e-12 (weights of 1 to fp32 rounding; the internal padding
+ *                    spheres, 1e15 away, must still underflow to weight 0).
+ *   mask_sharpness   finite and >= 0. The escape distances of the march (beyond which the mask is
+ *                    exactly 0 in fp32) assume a mask that vanishes outward; at 0 the mask is 0.5
+ *                    everywhere, every ray carries gradient and the escaped-ray exit is never armed.
+ *
+ * normal_eps and the normal. The reference takes the normal from six taps D(p +- eps e_a)
+ * (scene.rs:81-128): f_a = D(p + eps e_a) - D(p - eps e_a), n = f / sqrt(|f|^2 + 1e-6). The
+ * differentiable modes (rm_render_diff*, rm_train_step* and the ray / camera gradients) do not
+ * evaluate the taps: they use their limit as eps -> 0, f = 2 eps grad D, with grad D = sum_j
+ * beta_j (p - c_j) / rho_j, beta = softmax(-k delta), no term from a sphere under the clamp of
+ * scene.rs:72. normal_eps therefore still sets the length of n (|f| = 2 eps |grad D| against the
+ * 1e-6 under the root: |n| is about 0.2 at 1e-4), but not its curvature terms: the limit deviates
+ * from the taps by a relative amount that grows as (k eps)^2 (the taps' third-order term; D bends
+ * on the scale 1 / k where spheres blend). At the reference's 1e-4 that is below fp32 rounding. The suite holds the kernels to the reference's taps (fp64) up to
+ * k * normal_eps = 0.032, where the image differs between the two forms by less than a quarter of the
+ * forward bounds (1e-3 max, 1e-5 mean); at k * normal_eps = 0.32 it differs by more than the bounds,
+ * and there the suite holds the kernels to the limit form instead (tests/constants_ref.py).
+ * Masked |n.l(taps) - n.l(limit)| in fp64, max / mean over 24x24 rays of the final_1 camera, k = 32
+ * (tests/test_constants_reference.py re-measures it; at k = 5 the figures are 40 to 200 times smaller):
+ *   normal_eps         1e-4           1e-3           3e-3           1e-2           3e-2
+ *   scene.json         4e-8 / 8e-10   1.8e-5 / 3e-7  2.0e-4 / 3e-6  2.3e-3 / 3e-5  2.1e-2 / 3e-4
+ *   synthetic(48, 3)   2e-7 / 2e-9    2.2e-5 / 6e-7  2.9e-4 / 5e-6  3.7e-3 / 6e-5  2.9e-2 / 5e-4 */
 typedef struct rm_march {
   int32_t steps;          /* fixed march steps, renderer_diff.rs:22 (40)             */
   float smooth_k;         /* soft-min sharpness k, sdf.rs:30 (train 5->32, preview 32) */
-  float normal_eps;       /* finite-difference normal step, scene.rs:91 (1e-4)       */
+  float normal_eps;       /* finite-difference normal step, scene.rs:91 (1e-4); see above */
   float color_sharpness;  /* softmax(-c * dist) colour blend, renderer_diff.rs:74 (10) */
   float mask_sharpness;   /* sigmoid(-c * D) silhouette, renderer_diff.rs:88 (15)     */
   int32_t flags;          /* RM_MARCH_* bits (default 0)                              */

@@ -56,8 +56,15 @@ def burn_softmax(x, dim):
     return x / x.sum(dim=dim, keepdim=True)
 
 
-def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps=40):
-    """renderer_diff.rs:6-91 (steps is 40 in the reference; exposed for the configs)."""
+def _f32(x):
+    """A constant as rm_march holds it (fp32), so that EPS_F32 is the default's value."""
+    return float(torch.tensor(x, dtype=torch.float32))
+
+
+def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps=40, *,
+                normal_eps=EPS_F32, color_sharpness=10.0, mask_sharpness=15.0):
+    """renderer_diff.rs:6-91 (steps is 40 in the reference; exposed for the configs, as are the
+    reference's literals 1e-4, 10 and 15)."""
     n = ray_org.shape[0]
     t = torch.zeros((n, 1), dtype=ray_org.dtype)
     for _ in range(steps):
@@ -68,7 +75,7 @@ def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, s
     dist_last = scene_sdf_value(p_approx, centers, radius, smooth_k)
     t_final = t + dist_last
     p_final = ray_org + ray_dir * t_final
-    normal = calc_normal_scene(p_final.detach(), centers.detach(), radius.detach(), smooth_k)
+    normal = calc_normal_scene(p_final.detach(), centers.detach(), radius.detach(), smooth_k, eps=_f32(normal_eps))
     ld = light_dir
     ld_sq = ld.pow(2).sum()
     ld_norm = ld / ld_sq.sqrt()
@@ -81,11 +88,11 @@ def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, s
     p_dot_c = p_final @ centers.t()
     dists_sq = p_sq + c_sq - p_dot_c * 2.0
     dists = dists_sq.clamp_min(1e-6).sqrt() - radius.t()
-    weights = burn_softmax(dists * (-10.0), 1)
+    weights = burn_softmax(dists * (-_f32(color_sharpness)), 1)
     mixed = (colors.unsqueeze(0) * weights.unsqueeze(2)).sum(dim=1)
     object_color = mixed * lighting.unsqueeze(1)
     dist_scene = scene_sdf_value(p_final, centers, radius, smooth_k)
-    mask = torch.sigmoid(dist_scene * (-15.0))
+    mask = torch.sigmoid(dist_scene * (-_f32(mask_sharpness)))
     return object_color * mask
 
 

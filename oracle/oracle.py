@@ -50,6 +50,18 @@ def lib():
                 ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, real, _P]
             getattr(_lib, f"orc_render_{suf}").argtypes = [
                 ctypes.c_long, _P, _P, _P, _P, _P, ctypes.c_int, _P]
+            # the same entry points with normal_eps, color_sharpness, mask_sharpness and the normal's form
+            cs = [real, real, real, ctypes.c_int]
+            getattr(_lib, f"orc_render_diff_c_{suf}").argtypes = [
+                ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, real] + cs + [_P, _P]
+            getattr(_lib, f"orc_render_diff_backward_c_{suf}").argtypes = [
+                ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, real] + cs + [
+                _P, _P, _P, _P, _P, _P, _P]
+            getattr(_lib, f"orc_train_step_c_{suf}").argtypes = [
+                ctypes.c_long, _P, _P, _P, real, real, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int,
+                real] + cs + [_P, _P, _P, _P, _P, _P, _P]
+            getattr(_lib, f"orc_render_diff_debug_c_{suf}").argtypes = [
+                ctypes.c_long, _P, _P, _P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, real] + cs + [_P]
     return _lib
 
 
@@ -101,8 +113,23 @@ def _scene(scene, dt):
     return c, col, r, ld, a
 
 
-def render_diff(ray_org, ray_dir, scene, steps, smooth_k, precision="f64", with_t=False):
-    """renderer_diff.rs:6-91 forward on activated params. Returns out [N,3] (and t)."""
+NORMAL_EPS, COLOR_SHARPNESS, MASK_SHARPNESS = 1e-4, 10.0, 15.0  # scene.rs:91, renderer_diff.rs:74, :88
+
+
+def _consts(normal_eps, color_sharpness, mask_sharpness, normal):
+    """The four trailing arguments of the orc_*_c entry points. The constants are rounded to fp32
+    first, as rm_march holds them and as the reference builds its tap offsets (f32 literals), so the
+    fp64 instantiation computes with the numbers the kernels are given."""
+    if normal not in ("taps", "limit"):
+        raise ValueError(f"normal must be 'taps' or 'limit', got {normal!r}")
+    return (float(np.float32(normal_eps)), float(np.float32(color_sharpness)), float(np.float32(mask_sharpness)),
+            1 if normal == "limit" else 0)
+
+
+def render_diff(ray_org, ray_dir, scene, steps, smooth_k, precision="f64", with_t=False, *, normal_eps=NORMAL_EPS,
+                color_sharpness=COLOR_SHARPNESS, mask_sharpness=MASK_SHARPNESS, normal="taps"):
+    """renderer_diff.rs:6-91 forward on activated params. Returns out [N,3] (and t). normal:
+    "taps" (scene.rs:81-128, the reference) or "limit" (f = 2 eps grad D, the taps as eps -> 0)."""
     dt = _dt(precision)
     o = _arr(ray_org, dt)
     d = _arr(ray_dir, dt)
@@ -110,13 +137,14 @@ def render_diff(ray_org, ray_dir, scene, steps, smooth_k, precision="f64", with_
     n = o.shape[0]
     out = np.empty((n, 3), dt)
     t = np.empty((n,), dt)
-    getattr(lib(), f"orc_render_diff_{precision}")(n, _ptr(o), _ptr(d), _ptr(c), _ptr(col), _ptr(r), _ptr(ld),
-                                                   _ptr(a), c.shape[0], steps, float(smooth_k), _ptr(out),
-                                                   _ptr(t))
+    getattr(lib(), f"orc_render_diff_c_{precision}")(
+        n, _ptr(o), _ptr(d), _ptr(c), _ptr(col), _ptr(r), _ptr(ld), _ptr(a), c.shape[0], steps, float(smooth_k),
+        *_consts(normal_eps, color_sharpness, mask_sharpness, normal), _ptr(out), _ptr(t))
     return (out, t) if with_t else out
 
 
-def render_diff_debug(ray_org, ray_dir, scene, steps, smooth_k, precision="f64"):
+def render_diff_debug(ray_org, ray_dir, scene, steps, smooth_k, precision="f64", *, normal_eps=NORMAL_EPS,
+                      color_sharpness=COLOR_SHARPNESS, mask_sharpness=MASK_SHARPNESS, normal="taps"):
     """Per-ray intermediates [N,24] (layout of rm_debug_intermediates)."""
     dt = _dt(precision)
     o = _arr(ray_org, dt)
@@ -124,9 +152,9 @@ def render_diff_debug(ray_org, ray_dir, scene, steps, smooth_k, precision="f64")
     c, col, r, ld, a = _scene(scene, dt)
     n = o.shape[0]
     dbg = np.zeros((n, 24), dt)
-    getattr(lib(), f"orc_render_diff_debug_{precision}")(n, _ptr(o), _ptr(d), _ptr(c), _ptr(col), _ptr(r),
-                                                         _ptr(ld), _ptr(a), c.shape[0], steps, float(smooth_k),
-                                                         _ptr(dbg))
+    getattr(lib(), f"orc_render_diff_debug_c_{precision}")(
+        n, _ptr(o), _ptr(d), _ptr(c), _ptr(col), _ptr(r), _ptr(ld), _ptr(a), c.shape[0], steps, float(smooth_k),
+        *_consts(normal_eps, color_sharpness, mask_sharpness, normal), _ptr(dbg))
     return dbg
 
 
@@ -135,7 +163,9 @@ def _grads(m, dt):
             "light_dir": np.zeros((3,), dt), "ambient": np.zeros((1,), dt)}
 
 
-def render_diff_backward(ray_org, ray_dir, scene, steps, smooth_k, grad_out, precision="f64", t_march=None):
+def render_diff_backward(ray_org, ray_dir, scene, steps, smooth_k, grad_out, precision="f64", t_march=None, *,
+                         normal_eps=NORMAL_EPS, color_sharpness=COLOR_SHARPNESS, mask_sharpness=MASK_SHARPNESS,
+                         normal="taps"):
     """Analytic burn-autodiff backward of render_diff given g = dL/dout. Returns grads of
     the ACTIVATED params (centers, radius, colors, light_dir (raw), ambient)."""
     dt = _dt(precision)
@@ -146,14 +176,16 @@ def render_diff_backward(ray_org, ray_dir, scene, steps, smooth_k, grad_out, pre
     n, m = o.shape[0], c.shape[0]
     gr = _grads(m, dt)
     tm = _arr(t_march, dt) if t_march is not None else None
-    getattr(lib(), f"orc_render_diff_backward_{precision}")(
+    getattr(lib(), f"orc_render_diff_backward_c_{precision}")(
         n, _ptr(o), _ptr(d), _ptr(c), _ptr(col), _ptr(r), _ptr(ld), _ptr(a), m, steps, float(smooth_k),
-        _ptr(tm) if tm is not None else None, _ptr(g), _ptr(gr["centers"]), _ptr(gr["radius"]),
+        *_consts(normal_eps, color_sharpness, mask_sharpness, normal), _ptr(tm) if tm is not None else None,
+        _ptr(g), _ptr(gr["centers"]), _ptr(gr["radius"]),
         _ptr(gr["colors"]), _ptr(gr["light_dir"]), _ptr(gr["ambient"]))
     return gr
 
 
-def train_step(ray_org, ray_dir, targets, scene, steps, smooth_k, progress, inv_count=None, precision="f64"):
+def train_step(ray_org, ray_dir, targets, scene, steps, smooth_k, progress, inv_count=None, precision="f64", *,
+               normal_eps=NORMAL_EPS, color_sharpness=COLOR_SHARPNESS, mask_sharpness=MASK_SHARPNESS, normal="taps"):
     """Fused forward + compute_loss reconstruction seed (training.rs:17-34) + backward.
     Returns (out, loss_sum, grads); loss = loss_sum * inv_count."""
     dt = _dt(precision)
@@ -167,9 +199,10 @@ def train_step(ray_org, ray_dir, targets, scene, steps, smooth_k, progress, inv_
     out = np.empty((n, 3), dt)
     loss = np.zeros((1,), dt)
     gr = _grads(m, dt)
-    getattr(lib(), f"orc_train_step_{precision}")(
+    getattr(lib(), f"orc_train_step_c_{precision}")(
         n, _ptr(o), _ptr(d), _ptr(tg), float(progress), float(inv_count), _ptr(c), _ptr(col), _ptr(r),
-        _ptr(ld), _ptr(a), m, steps, float(smooth_k), _ptr(out), _ptr(loss), _ptr(gr["centers"]),
+        _ptr(ld), _ptr(a), m, steps, float(smooth_k), *_consts(normal_eps, color_sharpness, mask_sharpness, normal),
+        _ptr(out), _ptr(loss), _ptr(gr["centers"]),
         _ptr(gr["radius"]), _ptr(gr["colors"]), _ptr(gr["light_dir"]), _ptr(gr["ambient"]))
     return out, float(loss[0]), gr
 

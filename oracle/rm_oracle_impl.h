@@ -121,6 +121,19 @@ static REAL FN(scene_sdf)(const REAL p[3], const REAL* centers, const REAL* radi
 
 /* ---- forward ------------------------------------------------------------------ */
 
+/* The three shading constants (rm_march.normal_eps / color_sharpness / mask_sharpness; the
+ * reference hard-codes scene.rs:91 eps = 1e-4, renderer_diff.rs:74 10 and :88 15) and the form of
+ * the normal: 0 = the reference's six taps, 1 = their limit as eps -> 0, f = 2 eps grad D. */
+typedef struct {
+  REAL eps, csharp, msharp;
+  int limit;
+} FN(Consts);
+
+static FN(Consts) FN(default_consts)(void) {
+  FN(Consts) c = {RF(1e-4f), RF(10), RF(15), 0};
+  return c;
+}
+
 typedef struct {
   REAL t;          /* march t after S detached steps (renderer_diff.rs:20-26) */
   REAL pa[3];      /* p_approx (renderer_diff.rs:30) */
@@ -132,6 +145,7 @@ typedef struct {
   REAL ldn[3], ldlen;
   REAL sdot, diff, L;
   REAL wmax, wsum;  /* colour softmax normalizer over -10*delta (renderer_diff.rs:74) */
+  REAL dmin;        /* min_j delta_j at p_final */
   REAL mix[3];
   REAL bmax, bsum;  /* mask soft-min normalizer over -k*delta (renderer_diff.rs:86) */
   REAL Df, mu;
@@ -141,7 +155,7 @@ typedef struct {
 /* renderer_diff.rs:6-91 render_diff, one ray. */
 static void FN(forward_ray)(const REAL o[3], const REAL d[3], const REAL* centers, const REAL* colors,
                             const REAL* radius, const REAL ld[3], REAL amb, int M, int steps, REAL k,
-                            const REAL* t_in, FN(RayFwd) * f) {
+                            const REAL* t_in, const FN(Consts) * cs, FN(RayFwd) * f) {
   REAL t = RF(0);                                              /* renderer_diff.rs:20 */
   if (t_in) {
     t = *t_in;
@@ -157,14 +171,40 @@ static void FN(forward_ray)(const REAL o[3], const REAL d[3], const REAL* center
   f->tf = t + dlast;                                           /* renderer_diff.rs:36 */
   for (int i = 0; i < 3; ++i) f->p[i] = o[i] + d[i] * f->tf;   /* renderer_diff.rs:39 */
 
-  /* scene.rs:81-128 calc_normal_scene: taps +x,-x,+y,-y,+z,-z at eps = 1e-4 */
-  const REAL eps = RF(1e-4f);
+  /* scene.rs:81-128 calc_normal_scene: taps +x,-x,+y,-y,+z,-z at eps (1e-4 in the reference) */
+  const REAL eps = cs->eps;
   REAL dd[6];
-  for (int a = 0; a < 3; ++a) {
-    for (int sgn = 0; sgn < 2; ++sgn) {
-      REAL tap[3] = {f->p[0], f->p[1], f->p[2]};
-      tap[a] = tap[a] + (sgn == 0 ? eps : -eps);               /* scene.rs:104 */
-      dd[2 * a + sgn] = FN(scene_sdf)(tap, centers, radius, M, k, NULL, NULL);
+  if (!cs->limit) {
+    for (int a = 0; a < 3; ++a) {
+      for (int sgn = 0; sgn < 2; ++sgn) {
+        REAL tap[3] = {f->p[0], f->p[1], f->p[2]};
+        tap[a] = tap[a] + (sgn == 0 ? eps : -eps);             /* scene.rs:104 */
+        dd[2 * a + sgn] = FN(scene_sdf)(tap, centers, radius, M, k, NULL, NULL);
+      }
+    }
+  } else {
+    /* The taps' limit as eps -> 0: D(p + eps e_a) - D(p - eps e_a) -> 2 eps dD/dp_a, with
+     * grad D = sum_j beta_j (p - c_j) / rho_j, beta = softmax(-k delta), and no term from a
+     * sphere whose squared distance sits under the clamp of scene.rs:72 (its rho is constant). */
+    REAL psq0 = f->p[0] * f->p[0] + f->p[1] * f->p[1] + f->p[2] * f->p[2];
+    REAL mx = -INFINITY, zs = RF(0), gD[3] = {RF(0), RF(0), RF(0)};
+    for (int j = 0; j < M; ++j) {
+      REAL q = FN(rho_sq)(f->p, psq0, centers + 3 * j);
+      REAL v = (SQRT(FMAX(q, RF(1e-6))) - radius[j]) * (-k);
+      if (v > mx) mx = v;
+    }
+    for (int j = 0; j < M; ++j) {
+      const REAL* c = centers + 3 * j;
+      REAL q = FN(rho_sq)(f->p, psq0, c);
+      REAL rho = SQRT(FMAX(q, RF(1e-6)));
+      REAL e = EXP((rho - radius[j]) * (-k) - mx);
+      zs += e;
+      if (q >= RF(1e-6))
+        for (int a = 0; a < 3; ++a) gD[a] += e * ((f->p[a] - c[a]) / rho);
+    }
+    for (int a = 0; a < 3; ++a) {
+      dd[2 * a] = eps * (gD[a] / zs);
+      dd[2 * a + 1] = -dd[2 * a];
     }
   }
   for (int q = 0; q < 6; ++q) f->dd[q] = dd[q];
@@ -184,19 +224,21 @@ static void FN(forward_ray)(const REAL o[3], const REAL d[3], const REAL* center
 
   /* renderer_diff.rs:65-84: softmax(-10*delta) colour blend; :86-90 mask */
   REAL psq = f->p[0] * f->p[0] + f->p[1] * f->p[1] + f->p[2] * f->p[2];
-  REAL wmax = -INFINITY, bmax = -INFINITY;
+  REAL wmax = -INFINITY, bmax = -INFINITY, dmin = INFINITY;
   for (int j = 0; j < M; ++j) {
     REAL q = FN(rho_sq)(f->p, psq, centers + 3 * j);
     REAL dl = SQRT(FMAX(q, RF(1e-6))) - radius[j];
-    REAL vw = dl * RF(-10), vb = dl * (-k);
+    REAL vw = dl * (-cs->csharp), vb = dl * (-k);
     if (vw > wmax) wmax = vw;
     if (vb > bmax) bmax = vb;
+    if (dl < dmin) dmin = dl;
   }
+  f->dmin = dmin;
   REAL wsum = RF(0), bsum = RF(0), mix[3] = {RF(0), RF(0), RF(0)};
   for (int j = 0; j < M; ++j) {
     REAL q = FN(rho_sq)(f->p, psq, centers + 3 * j);
     REAL dl = SQRT(FMAX(q, RF(1e-6))) - radius[j];
-    REAL ew = EXP(dl * RF(-10) - wmax);
+    REAL ew = EXP(dl * (-cs->csharp) - wmax);
     wsum += ew;
     bsum += EXP(dl * (-k) - bmax);
     for (int c = 0; c < 3; ++c) mix[c] += ew * colors[3 * j + c];
@@ -207,7 +249,7 @@ static void FN(forward_ray)(const REAL o[3], const REAL d[3], const REAL* center
   f->bmax = bmax;
   f->bsum = FMAX(bsum, RF(1e-8));
   f->Df = (LOG(f->bsum) + bmax) / (-k);                        /* scene_sdf_value(p_final) */
-  f->mu = RF(1) / (RF(1) + EXP(-(f->Df * RF(-15))));           /* sigmoid(-15 D) */
+  f->mu = RF(1) / (RF(1) + EXP(-(f->Df * (-cs->msharp))));     /* sigmoid(-15 D) */
   for (int c = 0; c < 3; ++c) f->out[c] = f->mix[c] * f->L * f->mu; /* :84, :90 */
 }
 
@@ -228,7 +270,7 @@ typedef struct {
  * gradient. */
 static void FN(backward_ray)(const REAL d[3], const REAL* centers, const REAL* colors,
                              const REAL* radius, REAL amb, int M, REAL k, const FN(RayFwd) * f,
-                             const REAL g[3], FN(GradAcc) * acc) {
+                             const REAL g[3], const FN(Consts) * cs, FN(GradAcc) * acc) {
   REAL gm[3], gdotm = g[0] * f->mix[0] + g[1] * f->mix[1] + g[2] * f->mix[2];
   for (int c = 0; c < 3; ++c) gm[c] = g[c] * f->L * f->mu;
   REAL gL = gdotm * f->mu;
@@ -236,7 +278,7 @@ static void FN(backward_ray)(const REAL d[3], const REAL* centers, const REAL* c
   acc->gamb += gL * (RF(1) - f->diff);                         /* d L / d ambient */
   REAL gs = f->sdot >= RF(0) ? gL * (RF(1) - amb) : RF(0);     /* clamp_min passes at x >= 0 */
   for (int c = 0; c < 3; ++c) acc->gell[c] += gs * f->n[c];
-  REAL cmu = gmu * f->mu * (RF(1) - f->mu) * RF(-15);
+  REAL cmu = gmu * f->mu * (RF(1) - f->mu) * (-cs->msharp);
   REAL mg = f->mix[0] * gm[0] + f->mix[1] * gm[1] + f->mix[2] * gm[2];
 
   /* sweep at p_final: colour softmax + mask soft-min share delta_j */
@@ -247,11 +289,11 @@ static void FN(backward_ray)(const REAL d[3], const REAL* centers, const REAL* c
     REAL q = FN(rho_sq)(f->p, psq, c);
     REAL rho = SQRT(FMAX(q, RF(1e-6)));
     REAL dl = rho - radius[j];
-    REAL w = EXP(dl * RF(-10) - f->wmax) / f->wsum;
+    REAL w = EXP(dl * (-cs->csharp) - f->wmax) / f->wsum;
     REAL beta = EXP(dl * (-k) - f->bmax) / f->bsum;
     const REAL* col = colors + 3 * j;
     REAL cg = col[0] * gm[0] + col[1] * gm[1] + col[2] * gm[2];
-    REAL gdl = RF(-10) * w * (cg - mg) + cmu * beta;
+    REAL gdl = (-cs->csharp) * w * (cg - mg) + cmu * beta;
     for (int cc = 0; cc < 3; ++cc) acc->gcol[3 * j + cc] += w * gm[cc];
     acc->gr[j] -= gdl;
     if (q >= RF(1e-6)) {                                       /* clamp_min(1e-6) gate */
@@ -306,43 +348,72 @@ static void FN(finish_light)(const REAL ld[3], const REAL gell[3], REAL gld[3]) 
 }
 
 /* Forward over N rays (render_diff). t_march (nullable) receives the detached march t. */
-void FN(orc_render_diff)(long n, const REAL* org, const REAL* dir, const REAL* centers, const REAL* colors,
-                         const REAL* radius, const REAL* ld, const REAL* amb, int M, int steps, REAL k,
-                         REAL* out, REAL* t_march) {
+static void FN(render_diff_cs)(long n, const REAL* org, const REAL* dir, const REAL* centers, const REAL* colors,
+                               const REAL* radius, const REAL* ld, const REAL* amb, int M, int steps, REAL k,
+                               const FN(Consts) * cs, REAL* out, REAL* t_march) {
 #pragma omp parallel for schedule(dynamic, 64)
   for (long i = 0; i < n; ++i) {
     FN(RayFwd) f;
-    FN(forward_ray)(org + 3 * i, dir + 3 * i, centers, colors, radius, ld, amb[0], M, steps, k, NULL, &f);
+    FN(forward_ray)(org + 3 * i, dir + 3 * i, centers, colors, radius, ld, amb[0], M, steps, k, NULL, cs, &f);
     for (int c = 0; c < 3; ++c) out[3 * i + c] = f.out[c];
     if (t_march) t_march[i] = f.t;
   }
 }
 
+void FN(orc_render_diff)(long n, const REAL* org, const REAL* dir, const REAL* centers, const REAL* colors,
+                         const REAL* radius, const REAL* ld, const REAL* amb, int M, int steps, REAL k,
+                         REAL* out, REAL* t_march) {
+  const FN(Consts) cs = FN(default_consts)();
+  FN(render_diff_cs)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, &cs, out, t_march);
+}
+
+/* The same with the three constants and the normal's form given (limit: 0 taps, 1 limit). */
+void FN(orc_render_diff_c)(long n, const REAL* org, const REAL* dir, const REAL* centers, const REAL* colors,
+                           const REAL* radius, const REAL* ld, const REAL* amb, int M, int steps, REAL k,
+                           REAL eps, REAL csharp, REAL msharp, int limit, REAL* out, REAL* t_march) {
+  const FN(Consts) cs = {eps, csharp, msharp, limit};
+  FN(render_diff_cs)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, &cs, out, t_march);
+}
+
 /* Diagnostics twin of rm_debug_intermediates: dbg [N][24] = {t, t_final, n, lighting, mix,
  * D_final, mask, n.l, min delta, Zw (shifted at min delta), Zb (shifted), 0}. */
-void FN(orc_render_diff_debug)(long n, const REAL* org, const REAL* dir, const REAL* centers, const REAL* colors,
-                               const REAL* radius, const REAL* ld, const REAL* amb, int M, int steps, REAL k,
-                               REAL* dbg) {
+static void FN(render_diff_debug_cs)(long n, const REAL* org, const REAL* dir, const REAL* centers,
+                                     const REAL* colors, const REAL* radius, const REAL* ld, const REAL* amb,
+                                     int M, int steps, REAL k, const FN(Consts) * cs, REAL* dbg) {
 #pragma omp parallel for schedule(dynamic, 64)
   for (long i = 0; i < n; ++i) {
     FN(RayFwd) f;
-    FN(forward_ray)(org + 3 * i, dir + 3 * i, centers, colors, radius, ld, amb[0], M, steps, k, NULL, &f);
+    FN(forward_ray)(org + 3 * i, dir + 3 * i, centers, colors, radius, ld, amb[0], M, steps, k, NULL, cs, &f);
     REAL* q = dbg + 24 * i;
     q[0] = f.t; q[1] = f.tf; q[2] = f.n[0]; q[3] = f.n[1]; q[4] = f.n[2]; q[5] = f.L;
     q[6] = f.mix[0]; q[7] = f.mix[1]; q[8] = f.mix[2]; q[9] = f.Df; q[10] = f.mu; q[11] = f.sdot;
-    q[12] = f.wmax / RF(-10); q[13] = f.wsum; q[14] = f.bsum; q[15] = RF(0);
+    q[12] = cs->csharp != RF(0) ? f.wmax / (-cs->csharp) : f.dmin; q[13] = f.wsum; q[14] = f.bsum; q[15] = RF(0);
     for (int t = 0; t < 6; ++t) q[16 + t] = f.dd[t];
     q[22] = q[23] = RF(0);
   }
+}
+
+void FN(orc_render_diff_debug)(long n, const REAL* org, const REAL* dir, const REAL* centers, const REAL* colors,
+                               const REAL* radius, const REAL* ld, const REAL* amb, int M, int steps, REAL k,
+                               REAL* dbg) {
+  const FN(Consts) cs = FN(default_consts)();
+  FN(render_diff_debug_cs)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, &cs, dbg);
+}
+
+void FN(orc_render_diff_debug_c)(long n, const REAL* org, const REAL* dir, const REAL* centers, const REAL* colors,
+                                 const REAL* radius, const REAL* ld, const REAL* amb, int M, int steps, REAL k,
+                                 REAL eps, REAL csharp, REAL msharp, int limit, REAL* dbg) {
+  const FN(Consts) cs = {eps, csharp, msharp, limit};
+  FN(render_diff_debug_cs)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, &cs, dbg);
 }
 
 /* Shared body of backward / train step. mode 0: g given (grad_out); mode 1: loss seed
  * from targets. Gradients are OVERWRITTEN. loss_sum (mode 1) receives sum |diff|*W. */
 static void FN(bwd_common)(long n, const REAL* org, const REAL* dir, const REAL* centers, const REAL* colors,
                            const REAL* radius, const REAL* ld, const REAL* amb, int M, int steps, REAL k,
-                           const REAL* t_march, int mode, const REAL* grad_out, const REAL* targets,
-                           REAL progress, REAL inv_count, REAL* out, REAL* loss_sum, REAL* gc, REAL* gr,
-                           REAL* gcol, REAL* gld, REAL* gamb) {
+                           const FN(Consts) * cs, const REAL* t_march, int mode, const REAL* grad_out,
+                           const REAL* targets, REAL progress, REAL inv_count, REAL* out, REAL* loss_sum,
+                           REAL* gc, REAL* gr, REAL* gcol, REAL* gld, REAL* gamb) {
   memset(gc, 0, sizeof(REAL) * 3 * M);
   memset(gr, 0, sizeof(REAL) * M);
   memset(gcol, 0, sizeof(REAL) * 3 * M);
@@ -360,7 +431,7 @@ static void FN(bwd_common)(long n, const REAL* org, const REAL* dir, const REAL*
     for (long i = 0; i < n; ++i) {
       FN(RayFwd) f;
       FN(forward_ray)(org + 3 * i, dir + 3 * i, centers, colors, radius, ld, amb[0], M, steps, k,
-                      t_march ? t_march + i : NULL, &f);
+                      t_march ? t_march + i : NULL, cs, &f);
       REAL g[3];
       if (mode == 0) {
         for (int c = 0; c < 3; ++c) g[c] = grad_out[3 * i + c];
@@ -369,7 +440,7 @@ static void FN(bwd_common)(long n, const REAL* org, const REAL* dir, const REAL*
       }
       if (out)
         for (int c = 0; c < 3; ++c) out[3 * i + c] = f.out[c];
-      FN(backward_ray)(dir + 3 * i, centers, colors, radius, amb[0], M, k, &f, g, &acc);
+      FN(backward_ray)(dir + 3 * i, centers, colors, radius, amb[0], M, k, &f, g, cs, &acc);
     }
 #pragma omp critical
     {
@@ -394,7 +465,18 @@ void FN(orc_render_diff_backward)(long n, const REAL* org, const REAL* dir, cons
                                   const REAL* colors, const REAL* radius, const REAL* ld, const REAL* amb,
                                   int M, int steps, REAL k, const REAL* t_march, const REAL* grad_out,
                                   REAL* gc, REAL* gr, REAL* gcol, REAL* gld, REAL* gamb) {
-  FN(bwd_common)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, t_march, 0, grad_out, NULL,
+  const FN(Consts) cs = FN(default_consts)();
+  FN(bwd_common)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, &cs, t_march, 0, grad_out, NULL,
+                 RF(0), RF(0), NULL, NULL, gc, gr, gcol, gld, gamb);
+}
+
+void FN(orc_render_diff_backward_c)(long n, const REAL* org, const REAL* dir, const REAL* centers,
+                                    const REAL* colors, const REAL* radius, const REAL* ld, const REAL* amb,
+                                    int M, int steps, REAL k, REAL eps, REAL csharp, REAL msharp, int limit,
+                                    const REAL* t_march, const REAL* grad_out, REAL* gc, REAL* gr, REAL* gcol,
+                                    REAL* gld, REAL* gamb) {
+  const FN(Consts) cs = {eps, csharp, msharp, limit};
+  FN(bwd_common)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, &cs, t_march, 0, grad_out, NULL,
                  RF(0), RF(0), NULL, NULL, gc, gr, gcol, gld, gamb);
 }
 
@@ -403,7 +485,18 @@ void FN(orc_train_step)(long n, const REAL* org, const REAL* dir, const REAL* ta
                         REAL inv_count, const REAL* centers, const REAL* colors, const REAL* radius,
                         const REAL* ld, const REAL* amb, int M, int steps, REAL k, REAL* out, REAL* loss_sum,
                         REAL* gc, REAL* gr, REAL* gcol, REAL* gld, REAL* gamb) {
-  FN(bwd_common)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, NULL, 1, NULL, targets,
+  const FN(Consts) cs = FN(default_consts)();
+  FN(bwd_common)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, &cs, NULL, 1, NULL, targets,
+                 progress, inv_count, out, loss_sum, gc, gr, gcol, gld, gamb);
+}
+
+void FN(orc_train_step_c)(long n, const REAL* org, const REAL* dir, const REAL* targets, REAL progress,
+                          REAL inv_count, const REAL* centers, const REAL* colors, const REAL* radius,
+                          const REAL* ld, const REAL* amb, int M, int steps, REAL k, REAL eps, REAL csharp,
+                          REAL msharp, int limit, REAL* out, REAL* loss_sum, REAL* gc, REAL* gr, REAL* gcol,
+                          REAL* gld, REAL* gamb) {
+  const FN(Consts) cs = {eps, csharp, msharp, limit};
+  FN(bwd_common)(n, org, dir, centers, colors, radius, ld, amb, M, steps, k, &cs, NULL, 1, NULL, targets,
                  progress, inv_count, out, loss_sum, gc, gr, gcol, gld, gamb);
 }
 

@@ -345,22 +345,32 @@ def fp32_errors(name):
     return measures(run_oracle(case(name), "f32"), reference(name))
 
 
-@functools.lru_cache(maxsize=None)
-def bounds(name):
-    """{measure: max(existing bound, MARGIN x the fp32 oracle's error)} at a case."""
-    return {key: max(existing_bound(key), MARGIN * v) for key, v in fp32_errors(name).items()}
+def derive_bounds(errors):
+    """The bound rule: {measure: max(existing bound, MARGIN x the fp32 oracle's error)}."""
+    return {key: max(existing_bound(key), MARGIN * v) for key, v in errors.items()}
 
 
-def caps_hold(name):
-    """The measures whose derived bound breaks a cap (empty: the case is accepted)."""
+def broken_caps(bnd):
+    """The measures of a dict of derived bounds that break a cap."""
     bad = []
-    for key, b in bounds(name).items():
+    for key, b in bnd.items():
         if len(key) == 3 and key[1] not in PER_SPHERE:
             if b > CAP_GLOBAL:
                 bad.append((key, b))
         elif b > CAP_FACTOR * existing_bound(key):
             bad.append((key, b))
     return bad
+
+
+@functools.lru_cache(maxsize=None)
+def bounds(name):
+    """{measure: max(existing bound, MARGIN x the fp32 oracle's error)} at a case."""
+    return derive_bounds(fp32_errors(name))
+
+
+def caps_hold(name):
+    """The measures whose derived bound breaks a cap (empty: the case is accepted)."""
+    return broken_caps(bounds(name))
 
 
 def ratios(got, name):
@@ -423,10 +433,15 @@ def t_names():
     return tuple(n for n in names() if n.startswith(T_CASES))
 
 
+def t_rel_error(t, t_ref):
+    """|t - t_ref| / max(1, |t_ref|) per ray."""
+    t_ref = np.asarray(t_ref, np.float64).reshape(-1)
+    return np.abs(np.asarray(t, np.float64).reshape(-1) - t_ref) / np.maximum(1.0, np.abs(t_ref))
+
+
 def t_error(t, name):
     """|t - t_ref| / max(1, |t_ref|) per ray against the fp64 march distance."""
-    t_ref = np.asarray(reference(name)["t"], np.float64).reshape(-1)
-    return np.abs(np.asarray(t, np.float64).reshape(-1) - t_ref) / np.maximum(1.0, np.abs(t_ref))
+    return t_rel_error(t, reference(name)["t"])
 
 
 T_NOISE = 2.0 ** -24  # relative: one rounding of every input

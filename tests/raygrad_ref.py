@@ -50,11 +50,16 @@ def scene_t(sc, dtype=torch.float64):
             "ambient": torch.tensor(np.asarray(sc["ambient"], np.float64).reshape(1), dtype=dtype)}
 
 
-def _render(o, d, s, k, steps):
-    return ar.render_diff(o, d, s["centers"], s["colors"], s["radius"], s["light_dir"], s["ambient"], k, steps)
+DEFAULTS = {"normal_eps": ar.EPS_F32, "color_sharpness": 10.0, "mask_sharpness": 15.0}
 
 
-def ray_grads(o, d, sc, k, steps, gout, dtype=torch.float64, with_centers=False):
+def _render(o, d, s, k, steps, **consts):
+    """consts: normal_eps, color_sharpness, mask_sharpness (the reference's values by default)."""
+    return ar.render_diff(o, d, s["centers"], s["colors"], s["radius"], s["light_dir"], s["ambient"], k, steps,
+                          **consts)
+
+
+def ray_grads(o, d, sc, k, steps, gout, dtype=torch.float64, with_centers=False, **consts):
     """Autograd of sum(render_diff * gout) w.r.t. ray_org and ray_dir ([N,3] numpy each), in the
     reference's op order at `dtype`; with_centers adds dL/dcenters."""
     s = scene_t(sc, dtype)
@@ -62,27 +67,29 @@ def ray_grads(o, d, sc, k, steps, gout, dtype=torch.float64, with_centers=False)
     dd = torch.tensor(np.asarray(d, np.float64), dtype=dtype).requires_grad_()
     if with_centers:
         s["centers"].requires_grad_()
-    out = _render(ot, dd, s, k, steps)
+    out = _render(ot, dd, s, k, steps, **consts)
     (out * torch.tensor(np.asarray(gout, np.float64), dtype=dtype)).sum().backward()
     res = (ot.grad.double().numpy(), dd.grad.double().numpy())
     return res + (s["centers"].grad.double().numpy(),) if with_centers else res
 
 
-def camera_grads(cam, width, height, sc, k, steps, gout, dtype=torch.float64):
+def camera_grads(cam, width, height, sc, k, steps, gout, dtype=torch.float64, **consts):
     """Autograd of sum(render_diff(create_camera_rays(cam)) * gout) w.r.t. eye, target, fov_deg."""
     s = scene_t(sc, dtype)
     eye = torch.tensor(np.asarray(cam[0], np.float32).astype(np.float64), dtype=dtype).requires_grad_()
     tgt = torch.tensor(np.asarray(cam[1], np.float32).astype(np.float64), dtype=dtype).requires_grad_()
     fov = torch.tensor(float(np.float32(cam[2])), dtype=dtype).requires_grad_()
     o, d = camera_rays_t(width, height, eye, tgt, fov)
-    out = _render(o, d, s, k, steps)
+    out = _render(o, d, s, k, steps, **consts)
     (out * torch.tensor(np.asarray(gout, np.float64), dtype=dtype)).sum().backward()
     return eye.grad.double().numpy(), tgt.grad.double().numpy(), float(fov.grad)
 
 
-def closed_form_ray_grads(o, d, sc, k, steps, gout):
+def closed_form_ray_grads(o, d, sc, k, steps, gout, **consts):
     """The closed form the kernels implement, in fp64 without autograd: sweep 1 at p_f gives g_p,
     sweep 2 at p_a gives g_pa = (g_p . d) grad D(p_a); g_org = g_p + g_pa, g_dir = t_f g_p + t g_pa."""
+    cs = {key: ar._f32(consts.get(key, v)) for key, v in DEFAULTS.items()}
+    eps, csharp, msharp = cs["normal_eps"], cs["color_sharpness"], cs["mask_sharpness"]
     with torch.no_grad():
         s = scene_t(sc)
         c, col, r, ld, amb = s["centers"], s["colors"], s["radius"], s["light_dir"], s["ambient"]
@@ -104,18 +111,18 @@ def closed_form_ray_grads(o, d, sc, k, steps, gout):
         tf = t + ar.scene_sdf_value(pa, c, r, k)
         pf = o + d * tf
         q, rho, dl = dists(pf)
-        n = ar.calc_normal_scene(pf, c, r, k)
+        n = ar.calc_normal_scene(pf, c, r, k, eps=eps)
         sdot = n @ (ld / ld.pow(2).sum().sqrt())
         L = (amb + sdot.clamp_min(0.0) * (1.0 - amb)).unsqueeze(1)
-        w = torch.softmax(-10.0 * dl, dim=1)
+        w = torch.softmax(-csharp * dl, dim=1)
         beta = torch.softmax(-k * dl, dim=1)
         mix = w @ col
-        mu = torch.sigmoid(-15.0 * ar.scene_sdf_value(pf, c, r, k))
+        mu = torch.sigmoid(-msharp * ar.scene_sdf_value(pf, c, r, k))
         gm = g * L * mu
         gmu = (g * mix).sum(1, keepdim=True) * L
-        cmu = gmu * mu * (1.0 - mu) * (-15.0)
+        cmu = gmu * mu * (1.0 - mu) * (-msharp)
         mg = (mix * gm).sum(1, keepdim=True)
-        gdl = -10.0 * w * (gm @ col.t() - mg) + cmu * beta
+        gdl = -csharp * w * (gm @ col.t() - mg) + cmu * beta
         gate = (q >= 1e-6).double()
         unit = (pf.unsqueeze(1) - c.unsqueeze(0)) / rho.unsqueeze(2)
         gp = ((gdl * gate).unsqueeze(2) * unit).sum(1)
@@ -124,6 +131,43 @@ def closed_form_ray_grads(o, d, sc, k, steps, gout):
         unit_a = (pa.unsqueeze(1) - c.unsqueeze(0)) / rhoa.unsqueeze(2)
         gpa = gt * ((alpha * gate_a).unsqueeze(2) * unit_a).sum(1)
         return (gp + gpa).numpy(), (tf * gp + t * gpa).numpy()
+
+
+# ---- the per-ray measure ---------------------------------------------------------------------------
+# max |a - b| / max |b| over the whole [N,3] array lets a ray whose gradient is small next to the
+# largest be wrong by 100 %. Per ray: |a_i - b_i| / |b_i| (vector norms) for every ray whose reference
+# norm is at least floor x the largest, in the tiers of conftest.REL_ELEM["bwd"] (5e-2 from 1e-2 of the
+# largest, 1e-1 from 1e-3). torch fp32 in the reference's op order has its own figure (a grazing ray's
+# gradient is ill-conditioned), so the bound is max(tier, PER_RAY_MARGIN x torch fp32's figure at the
+# case), and at most PER_RAY_CAP x the tier -- envelope_ref's rule, MARGIN and CAP_FACTOR.
+PER_RAY_MARGIN = 4.0
+PER_RAY_CAP = 10.0
+
+
+def per_ray_errors(a, b, tiers):
+    """[(floor, worst |a_i - b_i| / |b_i| over the rays with |b_i| >= floor max|b|)] for [N,3] arrays."""
+    a, b = np.asarray(a, np.float64).reshape(-1, 3), np.asarray(b, np.float64).reshape(-1, 3)
+    nb = np.sqrt((b * b).sum(1))
+    err = np.sqrt(((a - b) ** 2).sum(1))
+    out = []
+    for floor, _ in tiers:
+        big = (nb >= floor * nb.max()) & (nb > 0)
+        out.append((floor, float((err[big] / nb[big]).max()) if big.any() else 0.0))
+    return out
+
+
+def per_ray_bounds(f32_errors, tiers):
+    """[(floor, bound, within the cap)] from torch fp32's per_ray_errors at the same case."""
+    return [(floor, max(rel, PER_RAY_MARGIN * e), PER_RAY_MARGIN * e <= PER_RAY_CAP * rel)
+            for (floor, e), (_, rel) in zip(f32_errors, tiers)]
+
+
+def per_ray_check(got, f32, ref, tiers):
+    """[(floor, the figure of `got`, its bound, torch fp32's figure, the bound is within the cap)] per
+    tier, for a device result and torch fp32's against the fp64 reference (all [N,3])."""
+    fe = per_ray_errors(f32, ref, tiers)
+    return [(floor, e, bound, f, ok) for (floor, e), (_, bound, ok), (_, f) in
+            zip(per_ray_errors(got, ref, tiers), per_ray_bounds(fe, tiers), fe)]
 
 
 def camera_tail(cam, width, height, g_org, g_dir):

@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 import raygrad_ref as rr
-from conftest import FINAL1_CAMERA, GOLDEN, GRAD_TOL, REL_L2, final1_scene, gpu_available, record_margin
+from conftest import FINAL1_CAMERA, GOLDEN, GRAD_TOL, REL_ELEM, REL_L2, final1_scene, gpu_available, record_margin
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
 
@@ -136,6 +136,12 @@ def test_ray_gradients_match_autograd(rm, oracle, name):
         record_margin(f"raygrad_torch_f32_relL2_{what}", fl, REL_L2["bwd"])
         assert norm <= GRAD_TOL, (name, what, "normwise", norm, "torch fp32", fn)
         assert rl2 <= REL_L2["bwd"], (name, what, "relL2", rl2, "torch fp32", fl)
+        # per ray (raygrad_ref.per_ray_errors): a ray that is small next to the largest is held too
+        for floor, err, bound, f32_err, cap_ok in rr.per_ray_check(got, f32, ref, REL_ELEM["bwd"]):
+            print(f"{name} {what}: rays >= {floor:g} of the largest: gpu {err:.3e} (bound {bound:.3g}) | torch fp32 {f32_err:.3e}")
+            record_margin(f"raygrad_per_ray{floor:g}_{what}", err, bound)
+            assert cap_ok, (name, what, floor, "torch fp32 breaks the cap", f32_err)
+            assert err <= bound, (name, what, f"per ray (|g| >= {floor:g} max)", err, bound, "torch fp32", f32_err)
     # escaped rays: exact zeros in the reference, exact zeros on the GPU
     assert (g_org[~nz] == 0).all() and (g_dir[~nz] == 0).all()
 

@@ -231,7 +231,7 @@ def test_small_and_general_kernel_agree(rm, oracle, monkeypatch):
         assert np.abs(a - b).max() <= 3e-3 * max(np.abs(b).max(), 1e-12), key
 
 
-def _iteration(torch, native, render, model, src, fg, nu, nf, sc, steps, fused, monkeypatch):
+def _iteration(torch, native, render, model, src, fg, nu, nf, sc, steps, fused, monkeypatch, march_kw=None):
     """`steps` training iterations (train.rs:169-198) through rm_train_iteration (fused: one launch
     when eligible), through rm_sample_batch + rm_train_step + rm_optimizer_step (fused False), or
     through rm_train_step_sampled + rm_optimizer_step (fused "sampled": a data-parallel rank's
@@ -253,7 +253,7 @@ def _iteration(torch, native, render, model, src, fg, nu, nf, sc, steps, fused, 
     out = []
     for it in range(1, steps + 1):
         k = 5.0 + 27.0 * it / steps
-        march = native.march_params(40, k)
+        march = native.march_params(40, k, **(march_kw or {}))  # march_kw: normal_eps, color_sharpness, mask_sharpness
         args = (o.shape[0], p(fg), fg.numel(), nu, nf, 11, 1, it, it / steps, 1.0 / (3 * n))
         if fused in ("prepared", "prepared_other_step"):
             # the optimizer's gradient-independent part in the sampled launch; "prepared_other_step"
