@@ -17,44 +17,11 @@ using namespace rmh;
 
 namespace {
 
-#define HIPCHK(call)                                                                            \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess) return fail(RMH_ERR_GPU, "%s: %s", #call, hipGetErrorString(e_));     \
-  } while (0)
-
 #define RMCHK(ctx, call)                                                                        \
   do {                                                                                          \
     int r_ = (call);                                                                            \
     if (r_ != RM_OK) return fail(RMH_ERR_GPU, "%s: %s", #call, rm_last_error(ctx));             \
   } while (0)
-
-// Device buffer owned by the host driver.
-// Page-locked host memory (the loss readback: an async copy the stream wait then covers)
-struct PinnedBuf {
-  void* p = nullptr;
-  ~PinnedBuf() {
-    if (p) (void)hipHostFree(p);
-  }
-  hipError_t alloc(size_t n) { return hipHostMalloc(&p, n, hipHostMallocDefault); }
-  float* f() const { return (float*)p; }
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t n) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = n;
-    return hipMalloc(&p, n ? n : 4);
-  }
-  float* f() const { return (float*)p; }
-  int32_t* i() const { return (int32_t*)p; }
-};
 
 // A rank that leaves rmh_train with an error releases its side of the collectives
 // (rmh_collective.abort: the RCCL one aborts its communicator). The other ranks learn of it through
@@ -102,27 +69,6 @@ int sync_stream(const Gpu& g, const rmh_collective* comm) {
   return RMH_OK;
 }
 
-// IEEE binary16, round to nearest even (the conversion torch's .half() and the optimizer's
-// colors_f16_out use), for the initial fp16 colours of a stage.
-uint16_t f32_to_f16(float x) {
-  uint32_t u;
-  std::memcpy(&u, &x, 4);
-  const uint32_t sign = (u >> 16) & 0x8000u;
-  const uint32_t ax = u & 0x7fffffffu;
-  if (ax >= 0x7f800000u) return (uint16_t)(sign | 0x7c00u | (ax > 0x7f800000u ? 0x200u : 0u));  // inf / nan
-  if (ax >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);  // rounds past 65504: inf
-  if (ax < 0x38800000u) {  // subnormal half (or zero): scale by 2^24 and round
-    float a;
-    std::memcpy(&a, &ax, 4);
-    return (uint16_t)(sign | (uint32_t)std::nearbyint(a * 16777216.0f));
-  }
-  const uint32_t mant = ax & 0x7fffffu;
-  uint32_t h = ((ax >> 23) - 112u) << 10 | (mant >> 13);
-  const uint32_t rest = mant & 0x1fffu;
-  if (rest > 0x1000u || (rest == 0x1000u && (h & 1u))) ++h;  // carries into the exponent correctly
-  return (uint16_t)(sign | h);
-}
-
 bool file_exists(const std::string& p) {
   FILE* f = std::fopen(p.c_str(), "rb");
   if (!f) return false;
@@ -149,30 +95,17 @@ void camera_struct(rm_camera& c, const float eye[3], const float target[3], floa
   c.fov_deg = fov;
 }
 
-// save_tiled_preview (train.rs:335-366): render_diff at k = 32 of the activated packed model,
-// whole image in one camera-mode launch (the reference chunks 4096 rays only to save VRAM).
-int preview_packed(Gpu& g, const float* act_dev, const uint16_t* colors_f16, int32_t M, int32_t W, int32_t H,
-                   int32_t steps, const std::string& path) {
-  rm_scene sc;
-  rm_scene_from_packed(act_dev, M, &sc);
-  rm_march m;
-  rm_march_default(&m);
-  m.steps = steps;
-  if (colors_f16) {  // an fp16-colour model previews with the colours it trains with
-    sc.colors = (const float*)colors_f16;
-    m.flags |= RM_MARCH_COLOR_F16;
-  }
-  m.smooth_k = 32.0f;
-  rm_camera cam;
-  const float eye[3] = {0.0f, 0.0f, -2.5f}, tgt[3] = {0.0f, 0.0f, 0.0f};  // train.rs:37-44
-  camera_struct(cam, eye, tgt, 50.0f);
+// One camera's render_diff image as a file: the whole image in one camera-mode launch (the
+// reference chunks 4096 rays only to save VRAM), copied to the host, waited for and saved.
+int render_to_file(Gpu& g, const rm_scene& sc, const rm_march& m, const rm_camera& cam, int32_t W, int32_t H,
+                   const char* path) {
   DevBuf out;
   HIPCHK(out.alloc(sizeof(float) * 3 * (size_t)W * H));
   RMCHK(g.ctx, rm_render_diff_camera(g.ctx, &cam, 1, W, H, &sc, &m, out.f(), nullptr));
   std::vector<float> host(3 * (size_t)W * H);
   HIPCHK(hipMemcpyAsync(host.data(), out.p, out.bytes, hipMemcpyDeviceToHost, g.stream));
   HIPCHK(hipStreamSynchronize(g.stream));
-  return rmh_image_save(path.c_str(), host.data(), W, H);
+  return rmh_image_save(path, host.data(), W, H);
 }
 
 // train.rs:210-262: centers raw, colours sigmoid, radii softplus (no +0.01), light raw,
@@ -183,6 +116,315 @@ int export_scene(const std::vector<float>& raw, int32_t M, const std::string& pa
   for (int32_t i = 0; i < M; ++i) rad[i] = softplus_f32(raw[6 * M + i]);
   const float amb = sigmoid_f32(raw[7 * M + 3]);
   return rmh_scene_save(path.c_str(), M, raw.data(), col.data(), rad.data(), raw.data() + 7 * M, &amb);
+}
+
+// scene.json for rmh_preview / rmh_view as the activated packed buffer [centers | colours | radii +
+// offset | light | ambient] on the device of `g`, which opens once the file has parsed. `act` is
+// the caller's: the asynchronous upload reads it.
+int load_scene(const char* scene_json, float radius_offset, int32_t device, Gpu& g, std::vector<float>& act,
+               DevBuf& d_act, rm_scene* sc) {
+  int32_t M = 0;
+  float *c = nullptr, *col = nullptr, *r = nullptr, ld[3], amb = 0.0f;
+  int rc = rmh_scene_load(scene_json, &M, &c, &col, &r, ld, &amb);
+  if (rc) return rc;
+  std::unique_ptr<float, void (*)(void*)> g1(c, std::free), g2(col, std::free), g3(r, std::free);
+  if (M < 1) return fail(RMH_ERR_FORMAT, "%s has no sphere", scene_json);
+  act.resize(7 * (size_t)M + 4);
+  std::memcpy(act.data(), c, sizeof(float) * 3 * M);
+  std::memcpy(act.data() + 3 * M, col, sizeof(float) * 3 * M);
+  for (int32_t i = 0; i < M; ++i) act[6 * M + i] = r[i] + radius_offset;  // viewer.rs draws the stored radii
+  std::memcpy(act.data() + 7 * M, ld, sizeof ld);
+  act[7 * M + 3] = amb;
+  if ((rc = g.open(device)) != RMH_OK) return rc;
+  HIPCHK(d_act.alloc(sizeof(float) * act.size()));
+  HIPCHK(hipMemcpyAsync(d_act.p, act.data(), d_act.bytes, hipMemcpyHostToDevice, g.stream));
+  rm_scene_from_packed(d_act.f(), M, sc);
+  return RMH_OK;
+}
+
+// ---- rmh_train's phases, in the order of train.rs ----
+
+bool leads(const rmh_collective* comm) { return !comm || comm->rank == 0; }  // logs, previews and scene.json
+
+// rank q's share of the batch (B/P rays per rank, the remainder spread)
+int32_t batch_share(const rmh_train_config* cfg, int32_t world, int32_t q) {
+  return cfg->batch / world + (q < cfg->batch % world ? 1 : 0);
+}
+
+// The training set (train.rs:62-96). The host arrays stay: the asynchronous uploads read them.
+struct TrainSet {
+  std::vector<float> h_org, h_dir, h_tgt;
+  std::unique_ptr<rmh_dataset, void (*)(rmh_dataset*)> ds{nullptr, rmh_dataset_destroy};
+  DevBuf d_org, d_dir, d_tgt, d_fg;  // d_fg: the foreground list of the dataset, for the device sampler
+  int64_t P = 0, n_fg_list = 0;
+  // Opens `g` once the files have loaded.
+  int load(const rmh_train_config* cfg, Gpu& g, bool verbose) {
+    const int32_t W = cfg->width, H = cfg->height;
+    rmh_camera_entry* cams = nullptr;
+    int32_t ncam = 0;
+    int rc = rmh_cameras_load(cfg->cameras_json, &cams, &ncam);
+    if (rc) return rc;
+    std::unique_ptr<rmh_camera_entry, void (*)(void*)> cams_guard(cams, std::free);
+    if (ncam < 1) return fail(RMH_ERR_FORMAT, "%s holds no camera", cfg->cameras_json);
+    const int64_t per_view = (int64_t)W * H;
+    P = per_view * ncam;
+    h_org.resize(3 * P), h_dir.resize(3 * P), h_tgt.resize(3 * P);
+    for (int32_t v = 0; v < ncam; ++v) {
+      rmh_camera_rays(W, H, cams[v].origin, cams[v].target, cams[v].fov, h_org.data() + 3 * per_view * v,
+                      h_dir.data() + 3 * per_view * v);
+      const std::string img = resolve_image(cfg->cameras_json, cams[v].file);
+      int32_t iw = 0, ih = 0;
+      float* lin = nullptr;
+      if ((rc = rmh_image_load(img.c_str(), &iw, &ih, &lin)) != RMH_OK) return rc;
+      std::unique_ptr<float, void (*)(void*)> lin_guard(lin, std::free);
+      if (iw != W || ih != H) return fail(RMH_ERR_FORMAT, "%s is %dx%d, expected %dx%d", img.c_str(), iw, ih, W, H);
+      std::memcpy(h_tgt.data() + 3 * per_view * v, lin, sizeof(float) * 3 * per_view);
+    }
+    rmh_dataset* ds_raw = nullptr;
+    if ((rc = rmh_dataset_create(h_tgt.data(), P, &ds_raw)) != RMH_OK) return rc;
+    ds.reset(ds_raw);
+    int64_t nfg = 0, nbg = 0;
+    rmh_dataset_counts(ds.get(), &nfg, &nbg);
+    if (verbose) {
+      std::printf("Total training pixels: %lld\n", (long long)P);
+      std::printf("Foreground pixels: %lld, Background pixels: %lld\n", (long long)nfg, (long long)nbg);
+    }
+    if ((rc = g.open(cfg->device)) != RMH_OK) return rc;
+    HIPCHK(d_org.alloc(sizeof(float) * 3 * P));
+    HIPCHK(d_dir.alloc(sizeof(float) * 3 * P));
+    HIPCHK(d_tgt.alloc(sizeof(float) * 3 * P));
+    HIPCHK(hipMemcpyAsync(d_org.p, h_org.data(), d_org.bytes, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(d_dir.p, h_dir.data(), d_dir.bytes, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemcpyAsync(d_tgt.p, h_tgt.data(), d_tgt.bytes, hipMemcpyHostToDevice, g.stream));
+    const int32_t* h_fg = nullptr;  // owned by ds
+    rmh_dataset_fg(ds.get(), &h_fg, &n_fg_list);
+    HIPCHK(d_fg.alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(n_fg_list, 1)));
+    if (n_fg_list > 0)
+      HIPCHK(hipMemcpyAsync(d_fg.p, h_fg, sizeof(int32_t) * n_fg_list, hipMemcpyHostToDevice, g.stream));
+    return RMH_OK;
+  }
+};
+
+// The schedule arithmetic of one step, as plain numbers: no allocation, no output.
+struct StepPlan {
+  float global_step, progress;  // float, as train.rs has them; the sampler's counter is (uint64_t)global_step
+  float smooth_k, uniform_ratio, inv_count;
+  int64_t n_uni, n_boost, n_global;  // this rank's draw; every rank's draws together
+  double lr;
+  bool last, read_loss;
+};
+
+StepPlan plan_step(const rmh_train_config* cfg, const rmh_dataset* ds, int32_t stage, int32_t step, int32_t world,
+                   int32_t rank, double base_lr) {
+  StepPlan p{};
+  p.global_step = (float)(stage * cfg->steps_per_stage + step);
+  p.progress = p.global_step / (float)(cfg->stages * cfg->steps_per_stage);
+  p.smooth_k = 5.0f + (cfg->max_smooth - 5.0f) * p.progress;  // train.rs:174
+  p.uniform_ratio = 0.8f - 0.4f * p.progress;                  // train.rs:176
+  // the count rule of sample_batch (dataset.rs:47-82) on every rank's share: the global ray count
+  // of this step and this rank's own draw (the device draws and gathers)
+  for (int32_t q = 0; q < world; ++q) {
+    int64_t qu = 0, qf = 0;
+    rmh_dataset_sample_count(ds, batch_share(cfg, world, q), p.uniform_ratio, &qu, &qf);
+    p.n_global += qu + qf;
+    if (q == rank) p.n_uni = qu, p.n_boost = qf;
+  }
+  // model.forward + compute_loss + backward (train.rs:182-190), mean over the n*3 elements
+  p.inv_count = 1.0f / (3.0f * (float)p.n_global);
+  p.lr = step > cfg->steps_per_stage / 2 ? base_lr * 0.2 : base_lr;  // train.rs:193-197
+  p.last = stage == cfg->stages - 1 && step == cfg->steps_per_stage;
+  p.read_loss = (cfg->log_every > 0 && rank == 0 && step % cfg->log_every == 0) || p.last;
+  return p;
+}
+
+// One generation's device state, freed when the stage's scope ends: after the stage's last wait.
+struct Stage {
+  int32_t M = 0;
+  size_t np = 0;  // 7 M + 4
+  // d_grad: [packed gradient (np) | loss sum | penalty]: the first np + 1 floats are the one all-reduce
+  DevBuf d_raw, d_act, d_grad, d_m, d_v, d_col_h;
+  float* d_loss = nullptr;     // d_grad + np
+  std::vector<_Float16> half;  // fp16-colour models: the activated colours the renders read (d_col_h), on the host
+  rm_scene sc;
+  rm_grads gr;
+  rm_march march;
+  std::vector<float> init_centers;
+  // Leaves uploads on the stream that read `raw`: the caller waits before it changes `raw`.
+  int begin(Gpu& g, const std::vector<float>& raw, int32_t M_, bool f16, int32_t B, int32_t march_steps) {
+    M = M_;
+    np = 7 * (size_t)M + 4;
+    HIPCHK(d_raw.alloc(sizeof(float) * np));
+    HIPCHK(d_act.alloc(sizeof(float) * np));
+    HIPCHK(d_grad.alloc(sizeof(float) * (np + 2)));
+    d_loss = d_grad.f() + np;
+    HIPCHK(d_m.alloc(sizeof(float) * np));
+    HIPCHK(d_v.alloc(sizeof(float) * np));
+    HIPCHK(hipMemcpyAsync(d_raw.p, raw.data(), sizeof(float) * np, hipMemcpyHostToDevice, g.stream));
+    HIPCHK(hipMemsetAsync(d_m.p, 0, d_m.bytes, g.stream));  // Adam re-created per stage (train.rs:160)
+    HIPCHK(hipMemsetAsync(d_v.p, 0, d_v.bytes, g.stream));
+    RMCHK(g.ctx, rm_scene_activate(g.ctx, d_raw.f(), M, d_act.f()));
+    rm_scene_from_packed(d_act.f(), M, &sc);
+    rm_grads_from_packed(d_grad.f(), M, &gr);
+    rm_march_default(&march);
+    march.steps = march_steps;
+    if (f16) {
+      std::vector<float> col(3 * (size_t)M);
+      half = std::vector<_Float16>(col.size());
+      HIPCHK(hipMemcpyAsync(col.data(), d_act.f() + 3 * M, sizeof(float) * col.size(), hipMemcpyDeviceToHost,
+                            g.stream));
+      HIPCHK(hipStreamSynchronize(g.stream));
+      // round to nearest even, as torch's .half() and the optimizer's colors_f16_out do
+      for (size_t i = 0; i < col.size(); ++i) half[i] = (_Float16)col[i];
+      HIPCHK(d_col_h.alloc(sizeof(_Float16) * half.size()));
+      HIPCHK(hipMemcpyAsync(d_col_h.p, half.data(), d_col_h.bytes, hipMemcpyHostToDevice, g.stream));
+      sc.colors = (const float*)d_col_h.p;
+      march.flags |= RM_MARCH_COLOR_F16;
+    }
+    RMCHK(g.ctx, rm_reserve(g.ctx, B, M));
+    init_centers = std::vector<float>(raw.begin(), raw.begin() + 3 * M);
+    return RMH_OK;
+  }
+};
+
+// One step on the stream. The penalty share of the loss costs a summation launch: its pointer is
+// passed only on the steps that read the loss.
+int train_step(Gpu& g, const rmh_train_config* cfg, const rmh_collective* comm, const TrainSet& ts, Stage& st,
+               const StepPlan& p, int32_t stage, int32_t step) {
+  // batches: rank-distinct streams of the device sampler, one counter value per step
+  const uint64_t sample_stream = 1 + 1000 * (uint64_t)(comm ? comm->rank : 0);
+  float* penalty = p.read_loss ? st.d_loss + 1 : nullptr;
+  st.march.smooth_k = p.smooth_k;
+  if (!comm && !cfg->color_f16) {
+    // one process, no collective: draw + render + backward + optimizer in one call (one launch for
+    // the small models of the schedule)
+    RMCHK(g.ctx, rm_train_iteration(g.ctx, ts.d_org.f(), ts.d_dir.f(), ts.d_tgt.f(), ts.P, ts.d_fg.i(), ts.n_fg_list,
+                                    p.n_uni, p.n_boost, cfg->seed, sample_stream, (uint64_t)p.global_step, p.progress,
+                                    p.inv_count, &st.march, st.d_act.f(), st.d_grad.f(), st.d_raw.f(), st.d_m.f(),
+                                    st.d_v.f(), st.M, step, (float)p.lr, cfg->weight_decay, 1, st.d_loss, penalty));
+    return RMH_OK;
+  }
+  // draw + render + backward (one launch for the small models, whose extra block also runs the
+  // optimizer's gradient-independent part), then the all-reduce, then the update
+  RMCHK(g.ctx, rm_train_step_sampled_prepared(g.ctx, ts.d_org.f(), ts.d_dir.f(), ts.d_tgt.f(), ts.P, ts.d_fg.i(),
+                                              ts.n_fg_list, p.n_uni, p.n_boost, cfg->seed, sample_stream,
+                                              (uint64_t)p.global_step, p.progress, p.inv_count, &st.sc, &st.march,
+                                              &st.gr, st.d_loss, st.d_raw.f(), step, 1, penalty));
+  if (comm) {
+    const int rc = comm->all_reduce_sum(comm->state, st.d_grad.f(), (int64_t)st.np + 1, g.stream);
+    if (rc != RMH_OK)
+      return fail(rc, "all-reduce of the gradient (stage %d, step %d): %s", stage, step, rmh_last_error());
+  }
+  if (cfg->color_f16)
+    RMCHK(g.ctx, rm_optimizer_step_f16(g.ctx, st.d_raw.f(), st.d_grad.f(), st.d_m.f(), st.d_v.f(), st.M, step,
+                                       (float)p.lr, cfg->weight_decay, 1, penalty, st.d_act.f(),
+                                       (uint16_t*)st.d_col_h.p));
+  else
+    RMCHK(g.ctx, rm_optimizer_step(g.ctx, st.d_raw.f(), st.d_grad.f(), st.d_m.f(), st.d_v.f(), st.M, step,
+                                   (float)p.lr, cfg->weight_decay, 1, penalty, st.d_act.f()));
+  return RMH_OK;
+}
+
+// The loss of a reporting step: into page-locked memory on the stream, one wait under the
+// watchdog, then rank 0's log line (log_bits: with the two sums' bits, for diagnosis).
+int report_loss(Gpu& g, const rmh_train_config* cfg, const rmh_collective* comm, const Stage& st, const StepPlan& p,
+                int32_t step, const PinnedBuf& h_loss, bool log_bits, float* loss) {
+  HIPCHK(hipMemcpyAsync(h_loss.p, st.d_loss, 2 * sizeof(float), hipMemcpyDeviceToHost, g.stream));
+  if (const int rc = sync_stream(g, comm); rc != RMH_OK) return rc;
+  const float* s = h_loss.f();
+  *loss = s[0] * p.inv_count + s[1];  // training.rs:34 + penalties
+  if (leads(comm) && cfg->log_every > 0 && step % cfg->log_every == 0) {
+    std::printf("  Step %d | Loss: %.5f | k: %.1f", step, *loss, p.smooth_k);
+    if (log_bits) {
+      uint32_t b[2];
+      std::memcpy(b, s, sizeof b);
+      std::printf(" | bits %08x %08x", b[0], b[1]);
+    }
+    std::printf("\n");
+  }
+  return RMH_OK;
+}
+
+// The end of a stage (train.rs:206-290), entered when the host has issued the stage's steps: the
+// last wait and the timing, the trained parameters into `raw` and to on_generation, rank 0's files.
+int end_stage(Gpu& g, const rmh_train_config* cfg, const rmh_collective* comm, const Stage& st, int32_t stage,
+              std::chrono::steady_clock::time_point t0, bool stage_times, std::vector<float>& raw, double* seconds) {
+  const auto t_enq = std::chrono::steady_clock::now();
+  int rc = sync_stream(g, comm);
+  if (rc != RMH_OK) return rc;
+  const auto t_end = std::chrono::steady_clock::now();
+  *seconds += std::chrono::duration<double>(t_end - t0).count();
+  if (stage_times)  // measurement: host issue vs drain
+    std::fprintf(stderr, "stage %d: issued in %.3f ms, drained %.3f ms later\n", stage + 1,
+                 1e3 * std::chrono::duration<double>(t_enq - t0).count(),
+                 1e3 * std::chrono::duration<double>(t_end - t_enq).count());
+  HIPCHK(hipMemcpy(raw.data(), st.d_raw.p, sizeof(float) * st.np, hipMemcpyDeviceToHost));
+  if (cfg->on_generation) cfg->on_generation(cfg->user, stage, st.M, raw.data());
+  const std::string out_dir = cfg->out_dir ? cfg->out_dir : "";
+  if (!leads(comm) || out_dir.empty()) return RMH_OK;
+  const bool final = stage == cfg->stages - 1;
+  if (final) {
+    if ((rc = export_scene(raw, st.M, join_path(out_dir, "scene.json"))) != RMH_OK) return rc;
+    if (cfg->log_every > 0) std::printf("  => Saved to scene.json (N = %d)\n", st.M);
+  }
+  if (!cfg->previews) return RMH_OK;
+  const std::string name = final ? "steps/final_1.png" : "steps/stage_" + std::to_string(stage) + ".png";
+  // save_tiled_preview (train.rs:335-366): render_diff at k = 32 of the scene view and march the
+  // stage trained with (an fp16-colour model previews with its fp16 colours)
+  rm_march m = st.march;
+  m.smooth_k = 32.0f;
+  rm_camera cam;
+  const float eye[3] = {0.0f, 0.0f, -2.5f}, tgt[3] = {0.0f, 0.0f, 0.0f};  // train.rs:37-44
+  camera_struct(cam, eye, tgt, 50.0f);
+  return render_to_file(g, st.sc, m, cam, cfg->width, cfg->height, join_path(out_dir, name).c_str());
+}
+
+// The next generation (prune & split, train.rs:300-328): `raw` and `M` become the next stage's.
+// Rank 0 decides it (rng is consumed there only). With a collective it reaches every rank in two
+// broadcasts on the stream, each followed by a wait under the watchdog:
+//   1. one float, the size M'. It is exact (M' <= 2 M <= 2^17) and doubles as the status word:
+//      -1 says that rank 0 failed in prune_and_split.
+//   2. the 7 M' + 4 raw parameters.
+// Rank 0 returns its own error only after broadcast 1 has told the others. One rank with a
+// collective takes the same path as many (the RCCL path is the same). The size checks come last.
+int next_generation(Gpu& g, const rmh_train_config* cfg, const rmh_collective* comm, const Stage& st, int32_t stage,
+                    rmh_rng* rng, std::vector<float>& raw, int32_t* M) {
+  // the growth knobs: 0 (a zeroed struct) = the reference's value, < 0 = no such condition
+  // (rmh_prune_and_split_ex takes 0 for that) -- ADVICE r04: a zeroed config is the reference rule
+  const float split_scale = cfg->split_scale == 0.0f ? 1.0f : std::max(cfg->split_scale, 0.0f);
+  const float split_move = cfg->split_move == 0.0f ? 0.05f : std::max(cfg->split_move, 0.0f);
+  std::vector<float> next(14 * (size_t)st.M + 4);
+  int32_t nextM = 0;
+  int rc, split_rc = RMH_OK;
+  if (leads(comm))
+    split_rc = rmh_prune_and_split_ex(raw.data(), st.M, st.init_centers.data(), stage, cfg->stages, split_scale,
+                                      split_move, cfg->max_spheres, rng, next.data(), &nextM);
+  if (split_rc != RMH_OK && !comm) return split_rc;
+  if (comm) {
+    DevBuf d_next;
+    HIPCHK(d_next.alloc(sizeof(float) * next.size()));
+    float fm = split_rc == RMH_OK ? (float)nextM : -1.0f;
+    HIPCHK(hipMemcpyAsync(d_next.p, &fm, sizeof fm, hipMemcpyHostToDevice, g.stream));
+    if ((rc = comm->broadcast(comm->state, d_next.f(), 1, 0, g.stream)) != RMH_OK)
+      return fail(rc, "broadcast of the next size: %s", rmh_last_error());
+    if ((rc = sync_stream(g, comm)) != RMH_OK) return rc;
+    HIPCHK(hipMemcpy(&fm, d_next.p, sizeof fm, hipMemcpyDeviceToHost));
+    nextM = (int32_t)fm;
+    if (split_rc != RMH_OK) return split_rc;
+    if (nextM < 0) return fail(RMH_ERR_GPU, "rank 0 failed in prune_and_split (stage %d)", stage);
+    if (nextM < 1 || 7 * (size_t)nextM + 4 > next.size()) return fail(RMH_ERR_GPU, "broadcast size %d", nextM);
+    const size_t nn = 7 * (size_t)nextM + 4;
+    if (leads(comm))
+      HIPCHK(hipMemcpyAsync(d_next.p, next.data(), sizeof(float) * nn, hipMemcpyHostToDevice, g.stream));
+    if ((rc = comm->broadcast(comm->state, d_next.f(), (int64_t)nn, 0, g.stream)) != RMH_OK)
+      return fail(rc, "broadcast of the next generation: %s", rmh_last_error());
+    if ((rc = sync_stream(g, comm)) != RMH_OK) return rc;
+    HIPCHK(hipMemcpy(next.data(), d_next.p, sizeof(float) * nn, hipMemcpyDeviceToHost));
+  }
+  if (nextM > RM_MAX_SPHERES) return fail(RMH_ERR_INVALID_ARG, "model grew past RM_MAX_SPHERES");
+  next.resize(7 * (size_t)nextM + 4);
+  raw.swap(next);
+  *M = nextM;
+  return RMH_OK;
 }
 
 }  // namespace
@@ -216,263 +458,55 @@ int rmh_train(const rmh_train_config* cfg, rmh_train_result* result, float* raw_
   if (cfg->width < 1 || cfg->height < 1 || cfg->stages < 1 || cfg->steps_per_stage < 1 || cfg->batch < 1 ||
       cfg->march_steps < 1 || std::isnan(cfg->split_scale) || std::isnan(cfg->split_move) || cfg->max_spheres < 0)
     return fail(RMH_ERR_INVALID_ARG, "bad training configuration");
-  const bool f16 = cfg->color_f16 != 0;
-  // the growth knobs: 0 (a zeroed struct) = the reference's value, < 0 = no such condition
-  // (rmh_prune_and_split_ex takes 0 for that) -- ADVICE r04: a zeroed config is the reference rule
-  const float split_scale = cfg->split_scale == 0.0f ? 1.0f : std::max(cfg->split_scale, 0.0f);
-  const float split_move = cfg->split_move == 0.0f ? 0.05f : std::max(cfg->split_move, 0.0f);
-  const int32_t W = cfg->width, H = cfg->height;
   const rmh_collective* comm = cfg->comm;
   const int32_t world = comm ? comm->world : 1, rank = comm ? comm->rank : 0;
   if (world < 1 || rank < 0 || rank >= world || (world > 1 && (!comm->all_reduce_sum || !comm->broadcast)))
     return fail(RMH_ERR_INVALID_ARG, "bad collective (rank %d of %d)", rank, world);
   if (cfg->batch < world) return fail(RMH_ERR_INVALID_ARG, "batch %d < %d ranks", cfg->batch, world);
-  const bool lead = rank == 0;  // logs, previews and scene.json
-  AbortOnError abort_guard;
-  abort_guard.comm = comm;
-  const bool verbose = cfg->log_every > 0 && lead;
+  AbortOnError abort_guard{comm};  // from here on every error return releases this rank's side
+  const bool verbose = cfg->log_every > 0 && rank == 0;
+  const char *e_bits = std::getenv("RMH_LOG_BITS"), *e_times = std::getenv("RMH_STAGE_TIMES");
+  const bool log_bits = e_bits && e_bits[0] == '1', stage_times = e_times && e_times[0] == '1';
 
-  // ---- 1. cameras and targets (train.rs:62-96) ----
-  rmh_camera_entry* cams = nullptr;
-  int32_t ncam = 0;
-  int rc = rmh_cameras_load(cfg->cameras_json, &cams, &ncam);
-  if (rc) return rc;
-  std::unique_ptr<rmh_camera_entry, void (*)(void*)> cams_guard(cams, std::free);
-  if (ncam < 1) return fail(RMH_ERR_FORMAT, "%s holds no camera", cfg->cameras_json);
-  const int64_t per_view = (int64_t)W * H;
-  const int64_t P = per_view * ncam;
-  std::vector<float> h_org(3 * P), h_dir(3 * P), h_tgt(3 * P);
-  for (int32_t v = 0; v < ncam; ++v) {
-    rmh_camera_rays(W, H, cams[v].origin, cams[v].target, cams[v].fov, h_org.data() + 3 * per_view * v,
-                    h_dir.data() + 3 * per_view * v);
-    const std::string img = resolve_image(cfg->cameras_json, cams[v].file);
-    int32_t iw = 0, ih = 0;
-    float* lin = nullptr;
-    if ((rc = rmh_image_load(img.c_str(), &iw, &ih, &lin)) != RMH_OK) return rc;
-    std::unique_ptr<float, void (*)(void*)> lin_guard(lin, std::free);
-    if (iw != W || ih != H) return fail(RMH_ERR_FORMAT, "%s is %dx%d, expected %dx%d", img.c_str(), iw, ih, W, H);
-    std::memcpy(h_tgt.data() + 3 * per_view * v, lin, sizeof(float) * 3 * per_view);
-  }
-  rmh_dataset* ds_raw = nullptr;
-  if ((rc = rmh_dataset_create(h_tgt.data(), P, &ds_raw)) != RMH_OK) return rc;
-  std::unique_ptr<rmh_dataset, void (*)(rmh_dataset*)> ds(ds_raw, rmh_dataset_destroy);
-  int64_t nfg = 0, nbg = 0;
-  rmh_dataset_counts(ds.get(), &nfg, &nbg);
-  if (verbose) {
-    std::printf("Total training pixels: %lld\n", (long long)P);
-    std::printf("Foreground pixels: %lld, Background pixels: %lld\n", (long long)nfg, (long long)nbg);
-  }
-
-  Gpu g;
-  if ((rc = g.open(cfg->device)) != RMH_OK) return rc;
-  DevBuf d_org, d_dir, d_tgt, d_fg;
-  HIPCHK(d_org.alloc(sizeof(float) * 3 * P));
-  HIPCHK(d_dir.alloc(sizeof(float) * 3 * P));
-  HIPCHK(d_tgt.alloc(sizeof(float) * 3 * P));
-  HIPCHK(hipMemcpyAsync(d_org.p, h_org.data(), d_org.bytes, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_dir.p, h_dir.data(), d_dir.bytes, hipMemcpyHostToDevice, g.stream));
-  HIPCHK(hipMemcpyAsync(d_tgt.p, h_tgt.data(), d_tgt.bytes, hipMemcpyHostToDevice, g.stream));
-  // this rank's share of the batch (B/P rays per rank, the remainder spread)
-  auto share = [&](int32_t q) { return cfg->batch / world + (q < cfg->batch % world ? 1 : 0); };
-  const int32_t B = share(rank);
-  // the foreground list of the dataset, for the device sampler (rm_train_step_sampled /
-  // rm_train_iteration draw the batch from it)
-  const int32_t* h_fg = nullptr;
-  int64_t n_fg_list = 0;
-  rmh_dataset_fg(ds.get(), &h_fg, &n_fg_list);
-  HIPCHK(d_fg.alloc(sizeof(int32_t) * (size_t)std::max<int64_t>(n_fg_list, 1)));
-  if (n_fg_list > 0) HIPCHK(hipMemcpyAsync(d_fg.p, h_fg, sizeof(int32_t) * n_fg_list, hipMemcpyHostToDevice, g.stream));
-  // batches: rank-distinct streams of the device sampler, one counter value per step
-  const uint64_t sample_stream = 1 + 1000 * (uint64_t)rank;
-  rmh_rng rng_split;
+  Gpu g;  // before the device buffers, which go first
+  TrainSet ts;
+  int rc = ts.load(cfg, g, verbose);
+  if (rc != RMH_OK) return rc;
+  rmh_rng rng_split;  // consumed on rank 0 only
   rmh_rng_seed(&rng_split, cfg->seed, 2);
-
-  // ---- 2. initial model (train.rs:100-126) ----
-  int32_t M = 7;
+  int32_t M = 7;  // initial model (train.rs:100-126)
   std::vector<float> raw(7 * M + 4);
   rmh_initial_model(raw.data());
-  const std::string out_dir = cfg->out_dir ? cfg->out_dir : "";
-  const float total_steps = (float)(cfg->stages * cfg->steps_per_stage);
-  float last_loss = 0.0f;
-  int32_t steps_done = 0;
-  double seconds = 0.0;
-
-  rm_march march;
-  rm_march_default(&march);
-  march.steps = cfg->march_steps;
-  if (f16) march.flags |= RM_MARCH_COLOR_F16;
+  rmh_train_result res{};
   PinnedBuf h_loss;  // the loss sum and penalty read back on reporting steps
   HIPCHK(h_loss.alloc(2 * sizeof(float)));
   if (verbose) std::printf("Start Multi-Stage Optimization...\n");
 
   for (int32_t stage = 0; stage < cfg->stages; ++stage) {
     if (verbose) std::printf("=== Stage %d/%d (N = %d) ===\n", stage + 1, cfg->stages, M);
-    const size_t np = 7 * (size_t)M + 4;
-    DevBuf d_raw, d_act, d_grad, d_m, d_v, d_col_h;
-    HIPCHK(d_raw.alloc(sizeof(float) * np));
-    HIPCHK(d_act.alloc(sizeof(float) * np));
-    // [packed gradient (np) | loss sum | penalty]: the first np + 1 floats are the one all-reduce
-    HIPCHK(d_grad.alloc(sizeof(float) * (np + 2)));
-    float* d_loss = d_grad.f() + np;
-    HIPCHK(d_m.alloc(sizeof(float) * np));
-    HIPCHK(d_v.alloc(sizeof(float) * np));
-    HIPCHK(hipMemcpyAsync(d_raw.p, raw.data(), sizeof(float) * np, hipMemcpyHostToDevice, g.stream));
-    HIPCHK(hipMemsetAsync(d_m.p, 0, d_m.bytes, g.stream));  // Adam re-created per stage (train.rs:160)
-    HIPCHK(hipMemsetAsync(d_v.p, 0, d_v.bytes, g.stream));
-    RMCHK(g.ctx, rm_scene_activate(g.ctx, d_raw.f(), M, d_act.f()));
-    uint16_t* col_h = nullptr;  // fp16-colour models: the activated colours the renders read
-    if (f16) {
-      std::vector<float> col(3 * (size_t)M);
-      std::vector<uint16_t> half(3 * (size_t)M);
-      HIPCHK(hipMemcpyAsync(col.data(), d_act.f() + 3 * M, sizeof(float) * col.size(), hipMemcpyDeviceToHost,
-                            g.stream));
-      HIPCHK(hipStreamSynchronize(g.stream));
-      for (size_t i = 0; i < col.size(); ++i) half[i] = f32_to_f16(col[i]);
-      HIPCHK(d_col_h.alloc(sizeof(uint16_t) * half.size()));
-      HIPCHK(hipMemcpyAsync(d_col_h.p, half.data(), d_col_h.bytes, hipMemcpyHostToDevice, g.stream));
-      col_h = (uint16_t*)d_col_h.p;
-    }
-    RMCHK(g.ctx, rm_reserve(g.ctx, B, M));
-    const std::vector<float> init_centers(raw.begin(), raw.begin() + 3 * M);
+    Stage st;
+    rc = st.begin(g, raw, M, cfg->color_f16 != 0, batch_share(cfg, world, rank), cfg->march_steps);
+    if (rc != RMH_OK || (rc = sync_stream(g, comm)) != RMH_OK) return rc;  // set-up ends here: the steps are timed
     const double base_lr = (double)cfg->base_lr * std::pow(0.6, stage);  // train.rs:166
-    rm_scene sc;
-    rm_scene_from_packed(d_act.f(), M, &sc);
-    if (f16) sc.colors = (const float*)col_h;
-    rm_grads gr;
-    rm_grads_from_packed(d_grad.f(), M, &gr);
-
-    if ((rc = sync_stream(g, comm)) != RMH_OK) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     for (int32_t step = 1; step <= cfg->steps_per_stage; ++step) {
-      const float global_step = (float)(stage * cfg->steps_per_stage + step);
-      const float progress = global_step / total_steps;
-      march.smooth_k = 5.0f + (cfg->max_smooth - 5.0f) * progress;  // train.rs:174
-      const float uniform_ratio = 0.8f - 0.4f * progress;             // train.rs:176
-      // sample_batch (dataset.rs:47-82) on the device: the count rule, then draw + gather
-      int64_t n_uni = 0, n_boost = 0;
-      rmh_dataset_sample_count(ds.get(), B, uniform_ratio, &n_uni, &n_boost);
-      // the global ray count of this step: every rank's share under the same count rule
-      int64_t n_global = 0;
-      for (int32_t q = 0; q < world; ++q) {
-        int64_t qu = 0, qf = 0;
-        rmh_dataset_sample_count(ds.get(), share(q), uniform_ratio, &qu, &qf);
-        n_global += qu + qf;
-      }
-      // model.forward + compute_loss + backward (train.rs:182-190), mean over the n*3 elements
-      const float inv_count = 1.0f / (3.0f * (float)n_global);
-      const double lr = step > cfg->steps_per_stage / 2 ? base_lr * 0.2 : base_lr;  // train.rs:193-197
-      const bool last = stage == cfg->stages - 1 && step == cfg->steps_per_stage;
-      const bool read_loss = (verbose && step % cfg->log_every == 0) || last;
-      if (!comm && !f16) {
-        // one process, no collective: draw + render + backward + optimizer in one call (one
-        // launch for the small models of the schedule; the penalty share only on reporting steps)
-        RMCHK(g.ctx, rm_train_iteration(g.ctx, d_org.f(), d_dir.f(), d_tgt.f(), P, d_fg.i(), n_fg_list, n_uni, n_boost,
-                                        cfg->seed, sample_stream, (uint64_t)global_step, progress, inv_count, &march,
-                                        d_act.f(), d_grad.f(), d_raw.f(), d_m.f(), d_v.f(), M, step, (float)lr,
-                                        cfg->weight_decay, 1, d_loss, read_loss ? d_loss + 1 : nullptr));
-      } else {
-        // draw + render + backward (one launch for the small models, whose extra block also runs
-        // the optimizer's gradient-independent part), then the all-reduce, then the update
-        RMCHK(g.ctx, rm_train_step_sampled_prepared(g.ctx, d_org.f(), d_dir.f(), d_tgt.f(), P, d_fg.i(), n_fg_list,
-                                                    n_uni, n_boost, cfg->seed, sample_stream, (uint64_t)global_step,
-                                                    progress, inv_count, &sc, &march, &gr, d_loss, d_raw.f(), step, 1,
-                                                    read_loss ? d_loss + 1 : nullptr));
-        if (comm && (rc = comm->all_reduce_sum(comm->state, d_grad.f(), (int64_t)np + 1, g.stream)) != RMH_OK)
-          return fail(rc, "all-reduce of the gradient (stage %d, step %d): %s", stage, step, rmh_last_error());
-        // the penalty share of the loss costs a summation launch: only on the steps that report it
-        if (f16)
-          RMCHK(g.ctx, rm_optimizer_step_f16(g.ctx, d_raw.f(), d_grad.f(), d_m.f(), d_v.f(), M, step, (float)lr,
-                                             cfg->weight_decay, 1, read_loss ? d_loss + 1 : nullptr, d_act.f(), col_h));
-        else
-          RMCHK(g.ctx, rm_optimizer_step(g.ctx, d_raw.f(), d_grad.f(), d_m.f(), d_v.f(), M, step, (float)lr,
-                                         cfg->weight_decay, 1, read_loss ? d_loss + 1 : nullptr, d_act.f()));
-      }
-      ++steps_done;
+      const StepPlan plan = plan_step(cfg, ts.ds.get(), stage, step, world, rank, base_lr);
+      if ((rc = train_step(g, cfg, comm, ts, st, plan, stage, step)) != RMH_OK) return rc;
+      ++res.steps;
       // With collectives every rank drains its stream under the watchdog every kStepsInFlight
       // steps, not only where rank 0 reads the loss: a rank whose peer stopped then meets the
       // watchdog within kStepsInFlight steps instead of blocking inside a launch or ncclAllReduce
       // once the HIP queue fills, and the watchdog's timeout measures at most that many steps of
       // queued work, not a whole stage's backlog.
-      if (comm && world > 1 && !read_loss && step % kStepsInFlight == 0 && (rc = sync_stream(g, comm)) != RMH_OK)
+      if (comm && world > 1 && !plan.read_loss && step % kStepsInFlight == 0 && (rc = sync_stream(g, comm)) != RMH_OK)
         return rc;
-      if (read_loss) {
-        // into page-locked memory on the stream, then one wait under the watchdog
-        HIPCHK(hipMemcpyAsync(h_loss.p, d_loss, 2 * sizeof(float), hipMemcpyDeviceToHost, g.stream));
-        if ((rc = sync_stream(g, comm)) != RMH_OK) return rc;
-        const float* s = h_loss.f();
-        last_loss = s[0] * inv_count + s[1];  // training.rs:34 + penalties
-        if (verbose && step % cfg->log_every == 0) {
-          std::printf("  Step %d | Loss: %.5f | k: %.1f", step, last_loss, march.smooth_k);
-          if (const char* e = std::getenv("RMH_LOG_BITS"); e && e[0] == '1') {  // diagnosis: the loss bits
-            uint32_t b[2];
-            std::memcpy(b, s, sizeof b);
-            std::printf(" | bits %08x %08x", b[0], b[1]);
-          }
-          std::printf("\n");
-        }
-      }
+      if (plan.read_loss &&
+          (rc = report_loss(g, cfg, comm, st, plan, step, h_loss, log_bits, &res.final_loss)) != RMH_OK)
+        return rc;
     }
-    const auto t_enq = std::chrono::steady_clock::now();  // the host has issued the stage's steps
-    if ((rc = sync_stream(g, comm)) != RMH_OK) return rc;
-    const auto t_end = std::chrono::steady_clock::now();
-    seconds += std::chrono::duration<double>(t_end - t0).count();
-    if (const char* e = std::getenv("RMH_STAGE_TIMES"); e && e[0] == '1')  // measurement: host issue vs drain
-      std::fprintf(stderr, "stage %d: issued in %.3f ms, drained %.3f ms later\n", stage + 1,
-                   1e3 * std::chrono::duration<double>(t_enq - t0).count(),
-                   1e3 * std::chrono::duration<double>(t_end - t_enq).count());
-    HIPCHK(hipMemcpy(raw.data(), d_raw.p, sizeof(float) * np, hipMemcpyDeviceToHost));
-    if (cfg->on_generation) cfg->on_generation(cfg->user, stage, M, raw.data());
-
-    if (stage == cfg->stages - 1) {  // train.rs:206-290
-      if (lead && !out_dir.empty()) {
-        if ((rc = export_scene(raw, M, join_path(out_dir, "scene.json"))) != RMH_OK) return rc;
-        if (verbose) std::printf("  => Saved to scene.json (N = %d)\n", M);
-        if (cfg->previews &&
-            (rc = preview_packed(g, d_act.f(), col_h, M, W, H, cfg->march_steps,
-                                 join_path(out_dir, "steps/final_1.png"))))
-          return rc;
-      }
-      break;
-    }
-    if (lead && cfg->previews && !out_dir.empty()) {
-      char name[64];
-      std::snprintf(name, sizeof name, "steps/stage_%d.png", stage);
-      if ((rc = preview_packed(g, d_act.f(), col_h, M, W, H, cfg->march_steps, join_path(out_dir, name)))) return rc;
-    }
-    // ---- C. prune & split (train.rs:300-328) ----
-    // rank 0 decides the next generation and broadcasts it: its size, then its raw params
-    std::vector<float> next(14 * (size_t)M + 4);
-    int32_t nextM = 0;
-    int split_rc = RMH_OK;
-    if (lead)
-      split_rc = rmh_prune_and_split_ex(raw.data(), M, init_centers.data(), stage, cfg->stages, split_scale,
-                                        split_move, cfg->max_spheres, &rng_split, next.data(), &nextM);
-    if (split_rc != RMH_OK && !comm) return split_rc;
-    if (comm) {  // (with one rank too: the RCCL path is the same)
-      DevBuf d_next;
-      HIPCHK(d_next.alloc(sizeof(float) * next.size()));
-      // the size doubles as the status word: -1 tells every rank that rank 0 failed
-      float fm = split_rc == RMH_OK ? (float)nextM : -1.0f;  // M' <= 2M <= 2^17: exact in fp32
-      HIPCHK(hipMemcpyAsync(d_next.p, &fm, sizeof fm, hipMemcpyHostToDevice, g.stream));
-      if ((rc = comm->broadcast(comm->state, d_next.f(), 1, 0, g.stream)) != RMH_OK)
-        return fail(rc, "broadcast of the next size: %s", rmh_last_error());
-      if ((rc = sync_stream(g, comm)) != RMH_OK) return rc;
-      HIPCHK(hipMemcpy(&fm, d_next.p, sizeof fm, hipMemcpyDeviceToHost));
-      nextM = (int32_t)fm;
-      if (split_rc != RMH_OK) return split_rc;  // rank 0, after telling the others
-      if (nextM < 0) return fail(RMH_ERR_GPU, "rank 0 failed in prune_and_split (stage %d)", stage);
-      if (nextM < 1 || 7 * (size_t)nextM + 4 > next.size()) return fail(RMH_ERR_GPU, "broadcast size %d", nextM);
-      const size_t nn = 7 * (size_t)nextM + 4;
-      if (lead) HIPCHK(hipMemcpyAsync(d_next.p, next.data(), sizeof(float) * nn, hipMemcpyHostToDevice, g.stream));
-      if ((rc = comm->broadcast(comm->state, d_next.f(), (int64_t)nn, 0, g.stream)) != RMH_OK)
-        return fail(rc, "broadcast of the next generation: %s", rmh_last_error());
-      if ((rc = sync_stream(g, comm)) != RMH_OK) return rc;
-      HIPCHK(hipMemcpy(next.data(), d_next.p, sizeof(float) * nn, hipMemcpyDeviceToHost));
-    }
-    if (nextM > RM_MAX_SPHERES) return fail(RMH_ERR_INVALID_ARG, "model grew past RM_MAX_SPHERES");
-    next.resize(7 * (size_t)nextM + 4);
-    raw.swap(next);
-    M = nextM;
+    if ((rc = end_stage(g, cfg, comm, st, stage, t0, stage_times, raw, &res.seconds)) != RMH_OK) return rc;
+    if (stage == cfg->stages - 1) break;
+    if ((rc = next_generation(g, cfg, comm, st, stage, &rng_split, raw, &M)) != RMH_OK) return rc;
     if (verbose) std::printf("  => Pruning & Splitting complete. Next N = %d\n", M);
   }
 
@@ -482,48 +516,26 @@ int rmh_train(const rmh_train_config* cfg, rmh_train_result* result, float* raw_
     std::memcpy(raw_out, raw.data(), sizeof(float) * (7 * (size_t)M + 4));
   }
   abort_guard.done = true;
-  if (result) {
-    result->num_spheres = M;
-    result->steps = steps_done;
-    result->final_loss = last_loss;
-    result->seconds = seconds;
-    result->step_ms = steps_done ? 1e3 * seconds / steps_done : 0.0;
-  }
+  res.num_spheres = M;
+  res.step_ms = res.steps ? 1e3 * res.seconds / res.steps : 0.0;
+  if (result) *result = res;
   return RMH_OK;
 }
 
 int rmh_preview(const char* scene_json, const char* png_path, int32_t W, int32_t H, const float eye[3],
                 const float target[3], float fov_deg, float radius_offset, int32_t device) {
   if (!scene_json || !png_path || !eye || !target || W < 1 || H < 1) return fail(RMH_ERR_INVALID_ARG, "bad arguments");
-  int32_t M = 0;
-  float *c = nullptr, *col = nullptr, *r = nullptr, ld[3], amb = 0.0f;
-  int rc = rmh_scene_load(scene_json, &M, &c, &col, &r, ld, &amb);
-  if (rc) return rc;
-  std::unique_ptr<float, void (*)(void*)> g1(c, std::free), g2(col, std::free), g3(r, std::free);
-  if (M < 1) return fail(RMH_ERR_FORMAT, "%s has no sphere", scene_json);
-  std::vector<float> act(7 * (size_t)M + 4);
-  std::memcpy(act.data(), c, sizeof(float) * 3 * M);
-  std::memcpy(act.data() + 3 * M, col, sizeof(float) * 3 * M);
-  for (int32_t i = 0; i < M; ++i) act[6 * M + i] = r[i] + radius_offset;
-  std::memcpy(act.data() + 7 * M, ld, sizeof ld);
-  act[7 * M + 3] = amb;
   Gpu g;
-  if ((rc = g.open(device)) != RMH_OK) return rc;
-  DevBuf d_act, out;
-  HIPCHK(d_act.alloc(sizeof(float) * act.size()));
-  HIPCHK(hipMemcpyAsync(d_act.p, act.data(), d_act.bytes, hipMemcpyHostToDevice, g.stream));
+  std::vector<float> act;
+  DevBuf d_act;
   rm_scene sc;
-  rm_scene_from_packed(d_act.f(), M, &sc);
+  const int rc = load_scene(scene_json, radius_offset, device, g, act, d_act, &sc);
+  if (rc) return rc;
   rm_march m;
   rm_march_default(&m);  // S = 40, k = 32 (train.rs:355)
   rm_camera cam;
   camera_struct(cam, eye, target, fov_deg);
-  HIPCHK(out.alloc(sizeof(float) * 3 * (size_t)W * H));
-  RMCHK(g.ctx, rm_render_diff_camera(g.ctx, &cam, 1, W, H, &sc, &m, out.f(), nullptr));
-  std::vector<float> host(3 * (size_t)W * H);
-  HIPCHK(hipMemcpyAsync(host.data(), out.p, out.bytes, hipMemcpyDeviceToHost, g.stream));
-  HIPCHK(hipStreamSynchronize(g.stream));
-  return rmh_image_save(png_path, host.data(), W, H);
+  return render_to_file(g, sc, m, cam, W, H, png_path);
 }
 
 void rmh_view_camera(const float pos[3], float yaw, float pitch, rmh_view_pose* out) {
@@ -552,25 +564,12 @@ int rmh_view(const char* scene_json, const char* out_pattern, int32_t W, int32_t
   static_assert(sizeof(rmh_view_pose) == sizeof(rm_view_camera), "rmh_view_pose is rm_view_camera");
   if (!scene_json || !out_pattern || !cams || W < 1 || H < 1 || count < 1)
     return fail(RMH_ERR_INVALID_ARG, "bad arguments");
-  int32_t M = 0;
-  float *c = nullptr, *col = nullptr, *r = nullptr, ld[3], amb = 0.0f;
-  int rc = rmh_scene_load(scene_json, &M, &c, &col, &r, ld, &amb);
-  if (rc) return rc;
-  std::unique_ptr<float, void (*)(void*)> g1(c, std::free), g2(col, std::free), g3(r, std::free);
-  if (M < 1) return fail(RMH_ERR_FORMAT, "%s has no sphere", scene_json);
-  std::vector<float> act(7 * (size_t)M + 4);
-  std::memcpy(act.data(), c, sizeof(float) * 3 * M);
-  std::memcpy(act.data() + 3 * M, col, sizeof(float) * 3 * M);
-  for (int32_t i = 0; i < M; ++i) act[6 * M + i] = r[i] + radius_offset;  // viewer.rs draws the stored radii
-  std::memcpy(act.data() + 7 * M, ld, sizeof ld);
-  act[7 * M + 3] = amb;
   Gpu g;
-  if ((rc = g.open(device)) != RMH_OK) return rc;
+  std::vector<float> act;
   DevBuf d_act, out;
-  HIPCHK(d_act.alloc(sizeof(float) * act.size()));
-  HIPCHK(hipMemcpyAsync(d_act.p, act.data(), d_act.bytes, hipMemcpyHostToDevice, g.stream));
   rm_scene sc;
-  rm_scene_from_packed(d_act.f(), M, &sc);
+  int rc = load_scene(scene_json, radius_offset, device, g, act, d_act, &sc);
+  if (rc) return rc;
   const size_t per_frame = 4 * (size_t)W * H;
   const int32_t chunk_max = std::min<int32_t>(count, RM_MAX_VIEWS_PER_CALL);
   HIPCHK(out.alloc(per_frame * chunk_max));

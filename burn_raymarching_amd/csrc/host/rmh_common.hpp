@@ -1,6 +1,8 @@
 // Internal helpers shared by the librm_host.so sources (include/rm_host.h is the API).
 #pragma once
 
+#include <hip/hip_runtime_api.h>
+
 #include <cstdarg>
 #include <cstdint>
 #include <map>
@@ -42,5 +44,40 @@ std::string fmt_f32(float x);
 // sigmoid / softplus(beta = 1) in f32, scene.rs:41-45 (softplus without the +0.01).
 float sigmoid_f32(float x);
 float softplus_f32(float x);
+
+// ---- HIP plumbing of the sources that drive the GPU ----------------------------------------
+// Returns fail(RMH_ERR_GPU, "<call>: <HIP error>") from the enclosing function when `call` fails.
+#define HIPCHK(call)                                                                                  \
+  do {                                                                                                \
+    hipError_t e_ = (call);                                                                           \
+    if (e_ != hipSuccess) return rmh::fail(RMH_ERR_GPU, "%s: %s", #call, hipGetErrorString(e_));      \
+  } while (0)
+
+// Page-locked host memory (the loss readback: an async copy the stream wait then covers)
+struct __attribute__((visibility("hidden"))) PinnedBuf {
+  void* p = nullptr;
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  hipError_t alloc(size_t n) { return hipHostMalloc(&p, n, hipHostMallocDefault); }
+  float* f() const { return (float*)p; }
+};
+
+// Device buffer owned by the host driver. (Both hidden: librm_host.so exports no C++ type of its own.)
+struct __attribute__((visibility("hidden"))) DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(size_t n) {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = n;
+    return hipMalloc(&p, n ? n : 4);
+  }
+  float* f() const { return (float*)p; }
+  int32_t* i() const { return (int32_t*)p; }
+};
 
 }  // namespace rmh
