@@ -104,6 +104,7 @@ struct KArgs {
                               // backward sweeps run for (non-zero seeds)
   float gone_d;               // > 0: rays that provably escape past this distance are `gone` (see the march)
   int early_exit;             // waves whose rays are all gone stop marching
+  int proof;                  // the escape proof before the march (rm_ray_kernel<.., PROOF>; march_policy)
   int split;                  // split march (RM_MARCH_SPLIT): 64 rays per block, a quarter of the spheres per wave
   int mfma;                   // march sums on the matrix cores (lse_mfma) instead of lse_weighted
   int shift_max;              // RM_MARCH_FORCE_MAX_SHIFT: every march step takes the running-max shift
@@ -210,8 +211,8 @@ typedef const __attribute__((address_space(4))) f4v* cf4_ptr;
 typedef const __attribute__((address_space(4))) f2v* cf2_ptr;
 typedef const __attribute__((address_space(4))) float* cf1_ptr;
 
-// Header after the records: {r_min, r_max, max |c_j - c_0|, 0, c_x, c_y, c_z, R} of the real
-// spheres ((c, R): bounding sphere, scene_bound), followed by one partial header per
+// Header after the records: {r_min, r_max, max |c_j - c_0|, R_soft, c_x, c_y, c_z, R} of the real
+// spheres ((c, R): bounding sphere, scene_bound; R_soft: soft_radius), followed by one partial header per
 // rm_prep_kernel block when that kernel ran on more than one block.
 constexpr int kRecHeader = 8;
 
@@ -416,6 +417,42 @@ __device__ __forceinline__ uint4 mfma_a_frag(const KArgs& a, int e) {
 __device__ __forceinline__ int mfma_w_sphere(int e) { return 16 * (e >> 5) + (e & 15); }
 __device__ __forceinline__ bool mfma_w_fixed(int e) { return (e & 16) != 0; }
 
+// The soft radius of the scene about c0 (hdr[3]; the escape proof's bound, bound_proof in
+// rm_ray_kernel): R_soft = (1/k) ln sum_j exp(k (|c_j - c0| + r_j)), rounded up. Every sphere has
+// |p - c_j| >= |p - c0| - |c_j - c0|, so exp(-k (|p - c_j| - r_j)) <= exp(-k |p - c0|)
+// exp(k (|c_j - c0| + r_j)); summed over j, the soft-min D(p) >= |p - c0| - R_soft at every p (the
+// padding spheres add 0 to D's sum in fp32, the clamp max(q, 1e-6) only raises D). R <= R_soft <=
+// R + ln(M)/k: the ball bound |p - c0| - R - ln(M)/k charges every sphere as if it sat at the rim.
+// In fp32, relative to R of scene_bound: v_j = (|c_j - c0| + r_j) (1 + 1e-5) + 1e-6 is scene_bound's
+// own rounded-up term, so v_j <= R and every exponent is <= 0; the sum (a term's relative error
+// below 2e-6 where it matters, at most M / 256 + 14 additions per chain) is taken 1e-5 up, the
+// logarithm's 1e-7 and the division go into the final 1e-5 relative + 1e-6. scratch as scene_bound's.
+// The escape proof runs from kProofMinSpheres (padded) spheres on: a bound step costs about a tenth
+// of a real march step at 64 spheres, and the C2 shape (256x256, 64 spheres, 10 views) ran 1.6 %
+// slower with the proof. A call without the proof (KArgs::proof, march_policy) launches the kernel
+// instance without it, and its record kernel skips the pass: hdr[3] = R + ln(M)/k, the ball's bound.
+constexpr int kProofMinSpheres = 128;
+__device__ __forceinline__ float soft_radius(const KArgs& a, float* scratch, int tid, const float c0[3], float R) {
+  const int lane = tid & 63, wave = tid >> 6, nt = (int)blockDim.x, nw = nt >> 6;
+  const float kappa = a.k * kLog2e;
+  float s = 0.0f;
+  for (int j = tid; j < a.M; j += nt) {
+    const float dx = a.centers[3 * j] - c0[0], dy = a.centers[3 * j + 1] - c0[1], dz = a.centers[3 * j + 2] - c0[2];
+    const float v = (fsqrt(dx * dx + dy * dy + dz * dz) + a.radius[j]) * (1.0f + 1e-5f) + 1e-6f;
+    s += fexp2(kappa * fminf(v - R, 0.0f));
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  if (lane == 0) scratch[8 * wave] = s;
+  __syncthreads();
+  float sum = scratch[0];
+  for (int w = 1; w < nw; ++w) sum += scratch[8 * w];
+  __syncthreads();  // scratch is reused by the caller
+  // sum >= 1 up to rounding (the sphere that sets R has exponent ~0); never above the ball's slack
+  const float rs = (R + flog2(fmaxf(sum, 1.0f) * (1.0f + 1e-5f)) / kappa) * (1.0f + 1e-5f) + 1e-6f;
+  return fminf(rs, R + a.lse_slack);
+}
+
 // hdr[4..7] = the bounding sphere (c, R) of scene_bound, for the march's escape test, and its
 // distance thresholds T(n), n < kEscTab: a receding ray at distance d from c with n march steps
 // left ends them at distance >= gone_d + R' from c if (1 - 1e-5) d >= T(n). Every step is at
@@ -428,7 +465,10 @@ __device__ void write_bound(const KArgs& a, float* hdr, float* esc) {
   __shared__ float scratch[8 * 16];
   float c[3], R;
   scene_bound(a, scratch, threadIdx.x, c, R);
+  const float rsoft = a.proof ? soft_radius(a, scratch, threadIdx.x, c, R)
+                                                                    : R + a.lse_slack;
   if (threadIdx.x == 0) {
+    hdr[3] = rsoft;
     hdr[4] = c[0];
     hdr[5] = c[1];
     hdr[6] = c[2];

@@ -622,6 +622,13 @@ bool launch_ray(bool cam, bool split, dim3 grid, size_t lds, hipStream_t st, con
       else hipExtLaunchKernelGGL((rm_ray_kernel<MODE, false, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
     }
   } else {
+    if constexpr (MODE != kRender) {
+      if (a.proof) {
+        if (cam) hipExtLaunchKernelGGL((rm_ray_kernel<MODE, true, false, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
+        else hipExtLaunchKernelGGL((rm_ray_kernel<MODE, false, false, true>), grid, blk, sh, st, ev0, ev1, 0u, a);
+        return true;
+      }
+    }
     if (cam) hipExtLaunchKernelGGL((rm_ray_kernel<MODE, true, false>), grid, blk, sh, st, ev0, ev1, 0u, a);
     else hipExtLaunchKernelGGL((rm_ray_kernel<MODE, false, false>), grid, blk, sh, st, ev0, ev1, 0u, a);
   }
@@ -670,6 +677,9 @@ bool march_policy(const Call& c, long long n, KArgs& a) {
     else if (a.msharp > 0.0f) a.gone_d = std::max(6.0f, 130.0f / (a.msharp * 1.44269504f));
   }
   a.early_exit = a.gone_d > 0.0f && (c.march->flags & RM_MARCH_NO_EARLY_EXIT) == 0 && !c.t_out ? 1 : 0;
+  // the escape proof (rm_ray.h, bound_proof): the unsplit training kernels with the exit on (hence no
+  // per-ray t and no debug output), from kProofMinSpheres spheres on
+  a.proof = a.early_exit && !split && c.mode != kRender && a.Mpad >= kProofMinSpheres ? 1 : 0;
   a.mfma = (c.march->flags & RM_MARCH_VALU_ONLY) == 0;
   a.shift_max = (c.march->flags & RM_MARCH_FORCE_MAX_SHIFT) != 0;
   if (c.mode == kRender) {  // renderer.rs:27-32, normalised in f32 on the host like the reference

@@ -126,19 +126,20 @@ __device__ __forceinline__ void add_cols4(float* rec, int j, const float (&v)[8]
   dst[0] = o;
 }
 
-template <int MODE, bool CAM, bool SPLIT>
+template <int MODE, bool CAM, bool SPLIT, bool PROOF>
 __device__ __forceinline__ void ray_body(const KArgs& a);
 
 // The per-ray kernel. Measurement build (-DRM_BLOCK_TRACE): every wave also records {start, end}
 // (s_memrealtime, 100 MHz), its hardware slot (HW_ID | XCC_ID << 32), {logical block, launch
 // position}, the times its march and its post-march forward ended and its march steps saved into
 // a.btrace[kTraceWords * (blockIdx.x * kWaves + wave) ...] (tools/block_trace.py).
-// SPLIT: the split march (RM_MARCH_SPLIT, KArgs::split).
-template <int MODE, bool CAM, bool SPLIT>
+// SPLIT: the split march (RM_MARCH_SPLIT, KArgs::split). PROOF: the escape proof before the march
+// (KArgs::proof; an instance of its own, so that a call without it runs the code it ran before).
+template <int MODE, bool CAM, bool SPLIT, bool PROOF>
 __device__ __forceinline__ void ray_entry(const KArgs& a) {
 #ifdef RM_BLOCK_TRACE
   const unsigned long long t_begin = __builtin_amdgcn_s_memrealtime();
-  ray_body<MODE, CAM, SPLIT>(a);
+  ray_body<MODE, CAM, SPLIT, PROOF>(a);
   const unsigned long long t_end = __builtin_amdgcn_s_memrealtime();
   if (a.btrace != nullptr && (threadIdx.x & 63) == 0) {
     const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
@@ -150,12 +151,13 @@ __device__ __forceinline__ void ray_entry(const KArgs& a) {
     r[3] = (unsigned long long)ray_block(a) | ((unsigned long long)blockIdx.x << 32);
   }
 #else
-  ray_body<MODE, CAM, SPLIT>(a);
+  ray_body<MODE, CAM, SPLIT, PROOF>(a);
 #endif
 }
-template <int MODE, bool CAM, bool SPLIT>
+template <int MODE, bool CAM, bool SPLIT, bool PROOF = false>
 __global__ __launch_bounds__(kBlock, SPLIT ? kSplitMinWaves : kMinWavesPerSimd) void rm_ray_kernel(const KArgs a) {
-  ray_entry<MODE, CAM, SPLIT>(a);
+  static_assert(!PROOF || (!SPLIT && MODE != kRender), "the escape proof: unsplit training kernels");
+  ray_entry<MODE, CAM, SPLIT, PROOF>(a);
 }
 
 // Split march (SPLIT): a block takes 64 rays (one 8x8 quadrant of a 16x16 tile in camera mode)
@@ -164,7 +166,7 @@ __global__ __launch_bounds__(kBlock, SPLIT ? kSplitMinWaves : kMinWavesPerSimd) 
 // the four waves march in lockstep through identical decisions (shift, clamp, exit). After the
 // march only wave 0 goes on (post-march forward, backward); the others end as escaped waves
 // with zero contributions. A ray that marches every step then occupies four SIMDs instead of one.
-template <int MODE, bool CAM, bool SPLIT>
+template <int MODE, bool CAM, bool SPLIT, bool PROOF>
 __device__ __forceinline__ void ray_body(const KArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const Lds L = bind_lds(a, smem);
@@ -528,6 +530,49 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     auto gone_finish = [&](int from) {
       if (gone && !retired) gone_steps(from);
     };
+    // Escape proof by a lower-bound march (exact; PROOF: the unsplit training kernels with the exit on,
+    // no per-ray t or debug output and at least kProofMinSpheres spheres; tried once, before the march's first loop step: a second try
+    // inside the loop proves more waves but costs the loop more than it saves, HISTORY.md §3).
+    // The step t <- t + D(p(t)) is monotone: D is 1-Lipschitz along the ray, so u <= t gives
+    // u + D(p(u)) <= t + D(p(t)). With any L <= D the bound trajectory u <- u + L(p(u)), started at
+    // the ray's t, therefore stays at or behind the ray step for step. Once the bound point recedes
+    // from c_0 at distance >= T(steps left) so does the ray, at least as far out: wave_escaped's test
+    // would hold for it at that step, and the ray ends gone. When that is proven for every ray of
+    // the wave that is not gone already, the wave stops here as it would have stopped there, with the
+    // same outputs (exactly 0). Otherwise nothing changes: a proven ray of a wave that marches on
+    // is not marked gone (gone rays leave the wave's votes, which would change other rays' bits).
+    // L = |p - c_0| - R_soft (soft_radius): the ball bound without the ln(M)/k that R' charges.
+    // Margins: R_soft carries the march's 1e-3 as R' does; another 1e-3 comes off every bound step
+    // and the distance test takes 2e-5 relative where wave_escaped takes 1e-5. They cover the bound
+    // march's own fp32 rounding: every value in it is at most B = |o|_1 + |c_0|_1 + 3 T(0) in
+    // magnitude (the bound march stops within a step of distance T(0), and a step at most doubles
+    // the distance), the proof is tried only where B <= 256 for every lane of the wave, and its five roundings per step are then
+    // below 256 x 6e-8 each, 1e-4 in all. A wave gives up once a ray's bound step falls to
+    // kProofMinStep (not to 0: a ray creeping along the ball is not proven in the steps left either,
+    // tools/escape_proof_sim.py): what the proof tries changes no result.
+    constexpr float kProofMinStep = 0.02f;
+    auto bound_proof = [&](int st) {
+      // a wave vote: origins differ per lane (array mode; a wave across two views), and every lane
+      // takes part in the votes below and must leave with the same answer (dead is wave-uniform)
+      if (__any(!(onorm + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= 256.0f))) return false;
+      const float rs = (hdr[3] + 1e-3f) * (1.0f + 1e-6f) + 1e-3f;
+      float u = t;
+      bool proven = gone || !valid;
+      for (int n = st; n < a.steps; ++n) {
+        const float ex = fmaf(d[0], u, o[0]) - c0x, ey = fmaf(d[1], u, o[1]) - c0y, ez = fmaf(d[2], u, o[2]) - c0z;
+        const float dist = fsqrt(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
+        const float Tn = esc_tab[min(a.steps - n, kEscTab - 1)];
+        proven = proven || (fmaf(ez, d[2], fmaf(ey, d[1], ex * d[0])) >= 0.0f && dist * (1.0f - 2e-5f) >= Tn);
+        if (__all(proven)) {
+          steps_saved += a.steps - st;
+          return true;
+        }
+        const float Lb = dist - rs;
+        if (__any(!proven && !(Lb > kProofMinStep))) return false;
+        u += proven ? 0.0f : Lb;
+      }
+      return false;
+    };
     int st_stop = -1;  // the step at which the march found every ray of the wave gone (not taken)
     int st0 = 0;
 #ifdef RM_BLOCK_TRACE
@@ -579,6 +624,9 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
         steps_saved = __float_as_int(cs.group(blk, 1));
       }
       st0 = a.cont_resume;
+    }
+    if constexpr (PROOF) {  // the host's choice (march_policy): exit on, no debug output, kProofMinSpheres
+      if (!dead && bound_proof(st0)) dead = true;
     }
     const unsigned long long below = (1ull << lane) - 1ull;
     for (int st = st0; !dead && st < a.steps; ++st) {
