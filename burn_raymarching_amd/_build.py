@@ -2,10 +2,10 @@
 
   burn_raymarching_amd/lib/libraymarch_hip.so  <- csrc/rm_kernels.hip   (the product: C ABI of include/raymarch.h;
                                                   one translation unit: the kernels in rm_kernels.hip and
-                                                  rm_{device,ray,reduce,small,raygrad,view}.h, the host side in
+                                                  rm_{device,ray,reduce,small,raygrad,view,sdf}.h, the host side in
                                                   rm_{context,launch,api}.h)
-  burn_raymarching_amd/lib/librm_host.so        <- csrc/host/{io,data,driver,comm}.cpp (C ABI of include/rm_host.h; RCCL)
-  burn_raymarching_amd/lib/rm_train             <- csrc/host/main.cpp    (CLI: train / generate / preview / view)
+  burn_raymarching_amd/lib/librm_host.so        <- csrc/host/{io,data,driver,comm,mesh}.cpp (C ABI of include/rm_host.h; RCCL)
+  burn_raymarching_amd/lib/rm_train             <- csrc/host/main.cpp    (CLI: train / generate / preview / view / mesh)
 
 Run ``python -m burn_raymarching_amd._build`` or ``__graft_entry__.build()``.
 """
@@ -46,6 +46,7 @@ def _stale(target: str, sources) -> bool:
 KERNEL_SOURCES = [os.path.join(CSRC, "rm_kernels.hip"), os.path.join(CSRC, "rm_device.h"),
                   os.path.join(CSRC, "rm_reduce.h"), os.path.join(CSRC, "rm_small.h"),
                   os.path.join(CSRC, "rm_raygrad.h"), os.path.join(CSRC, "rm_view.h"),
+                  os.path.join(CSRC, "rm_sdf.h"),
                   os.path.join(CSRC, "rm_ray.h"),
                   os.path.join(CSRC, "rm_context.h"),
                   os.path.join(CSRC, "rm_launch.h"), os.path.join(CSRC, "rm_api.h"),
@@ -77,7 +78,8 @@ HOST_DIR = os.path.join(CSRC, "host")
 EXE = os.path.join(LIBDIR, "rm_train")
 # librm_host.so's sources (rmh_version(): "host 0.1.0 src <hash>") and rm_train's ("rm_train src
 # <hash>"): each artefact carries the hash of what it was built from, as the kernel library does
-HOST_SOURCES = [os.path.join(HOST_DIR, f) for f in ("io.cpp", "data.cpp", "driver.cpp", "comm.cpp", "rmh_common.hpp")] + \
+HOST_SOURCES = [os.path.join(HOST_DIR, f) for f in ("io.cpp", "data.cpp", "driver.cpp", "comm.cpp", "mesh.cpp",
+                                                   "rmh_common.hpp")] + \
     [os.path.join(ROOT, "include", "rm_host.h"), os.path.join(ROOT, "include", "raymarch.h")]
 EXE_SOURCES = [os.path.join(HOST_DIR, "main.cpp"), os.path.join(ROOT, "include", "rm_host.h")]
 HOST_TAG = rb"host 0\.1\.0 src "

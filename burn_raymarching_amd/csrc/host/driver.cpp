@@ -598,6 +598,121 @@ int rmh_view(const char* scene_json, const char* out_pattern, int32_t W, int32_t
   return RMH_OK;
 }
 
+void rmh_mesh_config_default(rmh_mesh_config* c) {
+  if (!c) return;
+  c->res = 128;
+  c->margin = 0.05f;
+  c->smooth_k = 32.0f;      // train.rs:131 MAX_SMOOTH, the k of the previews and the viewer
+  c->radius_offset = 0.01f;  // scene.rs:43: the surface training fitted, as rmh_preview
+  c->refine = 2;
+  c->device = 0;
+}
+
+int rmh_mesh_extract(const char* scene_json, const rmh_mesh_config* config, rmh_mesh** out) {
+  if (!out) return fail(RMH_ERR_INVALID_ARG, "out is NULL");
+  *out = nullptr;
+  if (!scene_json) return fail(RMH_ERR_INVALID_ARG, "scene_json is NULL");
+  rmh_mesh_config cfg;
+  rmh_mesh_config_default(&cfg);
+  if (config) cfg = *config;
+  if (cfg.res < 1 || cfg.res > 2048) return fail(RMH_ERR_INVALID_ARG, "res %d out of [1, 2048]", cfg.res);
+  if (!(cfg.margin >= 0.0f) || !std::isfinite(cfg.margin) || !(cfg.smooth_k > 0.0f) || !std::isfinite(cfg.smooth_k) ||
+      !std::isfinite(cfg.radius_offset) || cfg.refine < 0 || cfg.refine > 64)
+    return fail(RMH_ERR_INVALID_ARG, "bad mesh configuration");
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t0) { return std::chrono::duration<double, std::milli>(clock::now() - t0).count(); };
+  Gpu g;
+  std::vector<float> act;
+  DevBuf d_act, d_grid, d_v, d_out;
+  rm_scene sc;
+  int rc = load_scene(scene_json, cfg.radius_offset, cfg.device, g, act, d_act, &sc);
+  if (rc) return rc;
+  const int32_t M = sc.num_spheres;
+
+  // the axis-aligned box of c_j +- (r_j + margin), cubic cells of (longest extent / res)
+  float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int32_t j = 0; j < M; ++j) {
+    const float reach = act[6 * M + j] + cfg.margin;
+    for (int k = 0; k < 3; ++k) {
+      lo[k] = std::min(lo[k], act[3 * j + k] - reach);
+      hi[k] = std::max(hi[k], act[3 * j + k] + reach);
+    }
+  }
+  const float longest = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+  if (!(longest > 0.0f) || !std::isfinite(longest)) return fail(RMH_ERR_FORMAT, "%s has no finite, non-empty box", scene_json);
+  const float spacing = longest / (float)cfg.res;
+  int32_t n[3];
+  for (int k = 0; k < 3; ++k)  // lattice points: the cells that cover the extent, at least one
+    n[k] = std::max(1, (int32_t)std::ceil((double)(hi[k] - lo[k]) / (double)spacing)) + 1;
+  const size_t cells = (size_t)n[0] * n[1] * n[2];
+
+  rm_sdf_params sp;
+  rm_sdf_params_default(&sp);
+  sp.smooth_k = cfg.smooth_k;
+  HIPCHK(d_grid.alloc(sizeof(float) * cells));
+  HIPCHK(hipStreamSynchronize(g.stream));  // the scene upload: not part of the grid's time
+  auto t0 = clock::now();
+  RMCHK(g.ctx, rm_sdf_grid(g.ctx, lo, spacing, n[0], n[1], n[2], &sc, &sp, d_grid.f(), nullptr));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  const double ms_grid = ms_since(t0);
+  t0 = clock::now();
+  std::vector<float> grid(cells);
+  HIPCHK(hipMemcpyAsync(grid.data(), d_grid.p, sizeof(float) * cells, hipMemcpyDeviceToHost, g.stream));
+  HIPCHK(hipStreamSynchronize(g.stream));
+  const double ms_copy = ms_since(t0);
+  t0 = clock::now();
+  rmh_mesh* raw = nullptr;
+  if ((rc = rmh_mesh_from_grid(grid.data(), n[0], n[1], n[2], lo, spacing, &raw)) != RMH_OK) return rc;
+  std::unique_ptr<rmh_mesh, void (*)(rmh_mesh*)> mesh(raw, rmh_mesh_free);
+  const double ms_extract = ms_since(t0);
+  t0 = clock::now();
+
+  const size_t V = mesh->vertices.size() / 3;
+  if (V > 0) {
+    // Newton projections onto D = 0, then the normals and colours at the final vertices
+    HIPCHK(d_v.alloc(sizeof(float) * 3 * V));
+    HIPCHK(d_out.alloc(sizeof(float) * 7 * V));  // dist [V] | grad [V][3] | color [V][3]
+    float *d_dist = d_out.f(), *d_grad = d_dist + V, *d_col = d_grad + 3 * V;
+    std::vector<float> h(7 * V);
+    for (int32_t it = 0; it <= cfg.refine; ++it) {
+      const bool last = it == cfg.refine;
+      HIPCHK(hipMemcpyAsync(d_v.p, mesh->vertices.data(), sizeof(float) * 3 * V, hipMemcpyHostToDevice, g.stream));
+      RMCHK(g.ctx, rm_sdf_query(g.ctx, d_v.f(), (int64_t)V, &sc, &sp, last ? nullptr : d_dist, d_grad, last ? d_col : nullptr));
+      HIPCHK(hipMemcpyAsync(h.data(), d_out.p, sizeof(float) * 7 * V, hipMemcpyDeviceToHost, g.stream));
+      HIPCHK(hipStreamSynchronize(g.stream));
+      const float* gr = h.data() + V;
+      if (!last) {
+        for (size_t v = 0; v < V; ++v) {
+          const float gx = gr[3 * v], gy = gr[3 * v + 1], gz = gr[3 * v + 2];
+          const float g2 = gx * gx + gy * gy + gz * gz;
+          if (!(g2 >= 1e-12f)) continue;
+          const float step = h[v] / g2;
+          mesh->vertices[3 * v] -= step * gx;
+          mesh->vertices[3 * v + 1] -= step * gy;
+          mesh->vertices[3 * v + 2] -= step * gz;
+        }
+      } else {
+        mesh->normals.assign(3 * V, 0.0f);
+        mesh->colors.assign(h.begin() + 4 * V, h.end());
+        for (size_t v = 0; v < V; ++v) {
+          const double gx = gr[3 * v], gy = gr[3 * v + 1], gz = gr[3 * v + 2];
+          const double len = std::sqrt(gx * gx + gy * gy + gz * gz);
+          if (!(len > 0.0)) continue;
+          mesh->normals[3 * v] = (float)(gx / len);
+          mesh->normals[3 * v + 1] = (float)(gy / len);
+          mesh->normals[3 * v + 2] = (float)(gz / len);
+        }
+      }
+    }
+  }
+  mesh->ms[0] = ms_grid;
+  mesh->ms[1] = ms_copy;
+  mesh->ms[2] = ms_extract;
+  mesh->ms[3] = ms_since(t0);
+  *out = mesh.release();
+  return RMH_OK;
+}
+
 int rmh_generate(const char* out_dir, const char* prefix, int32_t W, int32_t H, int32_t device) {
   if (!out_dir || W < 1 || H < 1) return fail(RMH_ERR_INVALID_ARG, "bad arguments");
   const std::string pre = prefix ? prefix : "";

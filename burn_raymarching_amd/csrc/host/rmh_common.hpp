@@ -12,6 +12,15 @@
 
 #include "rm_host.h"
 
+// The mesh behind rmh_mesh_* (mesh.cpp extracts it, driver.cpp's rmh_mesh_extract refines it and
+// fills the normals and colours).
+struct __attribute__((visibility("hidden"))) rmh_mesh {
+  std::vector<float> vertices, normals, colors;  // [V][3] each; normals / colors may be empty
+  std::vector<int32_t> faces;                    // [F][3]
+  int64_t open_edges = 0;
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};  // rmh_mesh_timing
+};
+
 namespace rmh {
 
 // Records the error text for rmh_last_error() and returns `code`.

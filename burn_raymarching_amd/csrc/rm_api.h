@@ -114,6 +114,15 @@ int sampled_step(rm_context* ctx, const float* ray_org, const float* ray_dir, co
                            counter, progress, inv_count, scene, march, grads, loss_sum);
 }
 
+// the parameters of rm_sdf_query / rm_sdf_grid (NULL: the defaults) and their flags
+int check_sdf_params(rm_context* ctx, const rm_sdf_params* params, rm_sdf_params& sp) {
+  rm_sdf_params_default(&sp);
+  if (params) sp = *params;
+  if ((sp.flags & ~RM_MARCH_COLOR_F16) != 0)
+    return fail(ctx, RM_ERR_INVALID_ARG, "flags 0x%x: the distance-field calls take RM_MARCH_COLOR_F16 only", sp.flags);
+  return RM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -691,6 +700,41 @@ int rm_view(rm_context* ctx, const rm_view_camera* cams, int32_t num_frames, int
   if (!std::isfinite(vp.focal) || !std::isfinite(vp.hit_eps) || !std::isfinite(vp.color_sharpness))
     return fail(ctx, RM_ERR_INVALID_ARG, "focal, hit_eps and color_sharpness must be finite");
   return run_view(ctx, cams, num_frames, width, height, scene, vp, out_rgb, out_rgba8, out_depth);
+}
+
+void rm_sdf_params_default(rm_sdf_params* p) {
+  if (!p) return;
+  p->smooth_k = 32.0f;         // train.rs:131 MAX_SMOOTH, the k of the previews and the viewer
+  p->color_sharpness = 10.0f;  // renderer_diff.rs:74
+  p->flags = 0;
+}
+
+int rm_sdf_query(rm_context* ctx, const float* points, int64_t num_points, const rm_scene* scene,
+                 const rm_sdf_params* params, float* dist, float* grad, float* color) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  rm_sdf_params sp;
+  int rc;
+  if ((rc = check_sdf_params(ctx, params, sp)) != RM_OK) return rc;
+  if (num_points < 0) return fail(ctx, RM_ERR_INVALID_ARG, "num_points %lld < 0", (long long)num_points);
+  if (!dist && !grad && !color) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
+  if (num_points > 0 && !points) return fail(ctx, RM_ERR_INVALID_ARG, "points is NULL");
+  return run_sdf(ctx, false, points, num_points, nullptr, 0.0f, 0, 0, scene, sp, dist, grad, color);
+}
+
+int rm_sdf_grid(rm_context* ctx, const float origin[3], float spacing, int32_t nx, int32_t ny, int32_t nz,
+                const rm_scene* scene, const rm_sdf_params* params, float* dist, float* color) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  rm_sdf_params sp;
+  int rc;
+  if ((rc = check_sdf_params(ctx, params, sp)) != RM_OK) return rc;
+  if (!origin || !std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+    return fail(ctx, RM_ERR_INVALID_ARG, "origin must be three finite floats");
+  if (!(spacing > 0.0f) || !std::isfinite(spacing))
+    return fail(ctx, RM_ERR_INVALID_ARG, "spacing must be finite and > 0 (got %g)", (double)spacing);
+  if (nx < 1 || ny < 1 || nz < 1 || (long long)nx * ny > (1LL << 34) / nz)
+    return fail(ctx, RM_ERR_INVALID_ARG, "bad grid extents %dx%dx%d", nx, ny, nz);
+  if (!dist && !color) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
+  return run_sdf(ctx, true, nullptr, (long long)nx * ny * nz, origin, spacing, nx, ny, scene, sp, dist, nullptr, color);
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // rm_launch.h -- launch orchestration behind the C ABI: what a call is (Geometry, Call,
 // RayGradCall), its checks and its KArgs, and the launch sequences of the general kernel (run),
 // the small-scene kernel (run_small), the ray-gradient kernel (run_raygrad), the viewer's frame
-// render (run_view) and the gradient reduction. Host code only; included by rm_kernels.hip after rm_context.h.
+// render (run_view), the distance-field query (run_sdf) and the gradient reduction. Host code only; included by rm_kernels.hip after rm_context.h.
 #pragma once
 
 namespace {
@@ -1098,6 +1098,65 @@ int run_view(rm_context* ctx, const rm_view_camera* cams, int frames, int W, int
     if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
     hipExtLaunchKernelGGL(rm_view_kernel, dim3(tiles, (unsigned)nf), dim3(kBlock), 0, ctx->stream, ev0, ev1, 0u, v);
     RM_HIP(ctx, hipGetLastError());
+  }
+  return RM_OK;
+}
+
+// ---- the distance-field query (rm_sdf.h) -----------------------------------------------------
+
+// The points of an rm_sdf_query (points, n) or the lattice of an rm_sdf_grid (grid: origin, spacing,
+// nx, ny; n = nx ny nz). All the scratch it takes is the record buffer (rm_reserve covers it).
+int run_sdf(rm_context* ctx, bool grid, const float* points, long long n, const float* origin, float spacing, int nx,
+            int ny, const rm_scene* scene, const rm_sdf_params& sp, float* dist, float* grad, float* color) {
+  ctx->opt_prepared = false;
+  int rc;
+  // the record kernel takes the scene and k through a march description
+  rm_march m;
+  rm_march_default(&m);
+  m.smooth_k = sp.smooth_k;
+  m.color_sharpness = sp.color_sharpness;
+  m.mask_sharpness = 0.0f;
+  m.flags = sp.flags & RM_MARCH_COLOR_F16;
+  Geometry g;
+  g.scene = scene;
+  g.march = &m;
+  if ((rc = check_scene(ctx, scene, false)) != RM_OK) return rc;
+  if ((rc = check_march(ctx, &m)) != RM_OK) return rc;
+  if (n == 0) return RM_OK;
+  KArgs a;
+  std::memset(&a, 0, sizeof a);
+  fill_scene_args(g, a);
+  if ((rc = prepare_records(ctx, a, false)) != RM_OK) return rc;
+
+  SdfArgs s;
+  std::memset(&s, 0, sizeof s);
+  s.rec_buf = a.rec_buf;
+  s.Mpad = a.Mpad;
+  s.kappa = sp.smooth_k * kLog2e;
+  s.c10l = a.csharp * kLog2e;
+  s.points = points;
+  s.n = n;
+  s.nx = nx;
+  s.ny = ny;
+  if (grid)
+    for (int k = 0; k < 3; ++k) s.origin[k] = origin[k];
+  s.spacing = spacing;
+  s.dist = dist;
+  s.grad = grad;
+  s.color = color;
+  const bool full = grad != nullptr || color != nullptr;
+  for (long long done = 0; done < n;) {
+    const long long nb = std::min<long long>((n - done + kBlock - 1) / kBlock, max_blocks_per_launch());
+    s.begin = done;
+    hipEvent_t ev0, ev1;
+    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
+    const dim3 gr((unsigned)nb), blk(kBlock);
+    if (grid && full) hipExtLaunchKernelGGL((rm_sdf_kernel<true, true>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, s);
+    else if (grid) hipExtLaunchKernelGGL((rm_sdf_kernel<true, false>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, s);
+    else if (full) hipExtLaunchKernelGGL((rm_sdf_kernel<false, true>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, s);
+    else hipExtLaunchKernelGGL((rm_sdf_kernel<false, false>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, s);
+    RM_HIP(ctx, hipGetLastError());
+    done += nb * kBlock;
   }
   return RM_OK;
 }

@@ -71,6 +71,11 @@ class RmhViewPose(ctypes.Structure):
     _fields_ = [("pos", ctypes.c_float * 3), ("forward", ctypes.c_float * 3), ("up", ctypes.c_float * 3)]
 
 
+class RmhMeshConfig(ctypes.Structure):
+    _fields_ = [("res", ctypes.c_int32), ("margin", ctypes.c_float), ("smooth_k", ctypes.c_float),
+                ("radius_offset", ctypes.c_float), ("refine", ctypes.c_int32), ("device", ctypes.c_int32)]
+
+
 _P = ctypes.c_void_p
 _I32 = ctypes.c_int32
 _I64 = ctypes.c_int64
@@ -119,6 +124,17 @@ SIGNATURES = {
     "rmh_view": (ctypes.c_int, [_S, _S, _I32, _I32, ctypes.POINTER(RmhViewPose), _I32, _F, _I32]),
     "rmh_png_write_rgba": (ctypes.c_int, [_S, _P, _I32, _I32]),
     "rmh_png_read_rgba": (ctypes.c_int, [_S, _PI32, _PI32, _PP]),
+    "rmh_mesh_from_grid": (ctypes.c_int, [_P, _I32, _I32, _I32, _P, _F, _PP]),
+    "rmh_mesh_config_default": (None, [ctypes.POINTER(RmhMeshConfig)]),
+    "rmh_mesh_extract": (ctypes.c_int, [_S, ctypes.POINTER(RmhMeshConfig), _PP]),
+    "rmh_mesh_counts": (None, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "rmh_mesh_vertices": (_P, [_P]),
+    "rmh_mesh_normals": (_P, [_P]),
+    "rmh_mesh_colors": (_P, [_P]),
+    "rmh_mesh_faces": (_P, [_P]),
+    "rmh_mesh_timing": (None, [_P, ctypes.POINTER(ctypes.c_double * 4)]),
+    "rmh_mesh_free": (None, [_P]),
+    "rmh_mesh_write_ply": (ctypes.c_int, [_P, _S]),
     "rmh_generate": (ctypes.c_int, [_S, _S, _I32, _I32, _I32]),
     "rmh_version": (ctypes.c_char_p, []),
 }
@@ -481,3 +497,75 @@ def png_write_rgba(path, rgba: np.ndarray) -> None:
 
 def generate(out_dir, prefix="data/", width=256, height=256, device=0) -> None:
     _check(lib().rmh_generate(_b(out_dir), prefix.encode(), width, height, device), "rmh_generate")
+
+
+# ---- the trained surface as a mesh ---------------------------------------------------------
+class Mesh:
+    """An rmh_mesh: `vertices` [V, 3] float32, `faces` [F, 3] int32, `open_edges` (edges not shared
+    by exactly two triangles: non-zero only where the surface leaves the grid), and for a mesh of
+    mesh_extract `normals` [V, 3] (unit) and `colors` [V, 3] (linear RGB), else None; `timing_ms` =
+    (grid, copy, extraction, refinement). The arrays are read-only copies; the handle stays for
+    mesh_write_ply."""
+
+    def __init__(self, handle):
+        self.h = handle
+        nv, nf, ne = _I64(), _I64(), _I64()
+        lib().rmh_mesh_counts(self.h, ctypes.byref(nv), ctypes.byref(nf), ctypes.byref(ne))
+        self.open_edges = ne.value
+
+        def grab(ptr, n, dtype):
+            if not ptr:
+                return None if n else np.zeros((0, 3), dtype)
+            a = np.frombuffer(ctypes.string_at(ptr, n * 3 * np.dtype(dtype).itemsize), dtype=dtype).reshape(n, 3)
+            return a
+
+        self.vertices = grab(lib().rmh_mesh_vertices(self.h), nv.value, np.float32)
+        self.faces = grab(lib().rmh_mesh_faces(self.h), nf.value, np.int32)
+        pn, pc = lib().rmh_mesh_normals(self.h), lib().rmh_mesh_colors(self.h)
+        self.normals = grab(pn, nv.value, np.float32) if pn else None
+        self.colors = grab(pc, nv.value, np.float32) if pc else None
+        ms = (ctypes.c_double * 4)()
+        lib().rmh_mesh_timing(self.h, ctypes.byref(ms))
+        self.timing_ms = tuple(ms)
+
+    def close(self):
+        if self.h:
+            lib().rmh_mesh_free(self.h)
+            self.h = _P()
+
+    __del__ = close
+
+
+def mesh_from_grid(dist, origin, spacing) -> Mesh:
+    """rmh_mesh_from_grid: marching tetrahedra (Kuhn decomposition) on dist [nz, ny, nx] (x fastest,
+    what render.sdf_grid returns), lattice point i at origin + float32(i) * spacing, inside where
+    D < 0. CPU only."""
+    d = _f32c(dist)
+    if d.ndim != 3:
+        raise ValueError("dist must be [nz, ny, nx]")
+    o = _f32c(origin, (3,))
+    h = _P()
+    _check(lib().rmh_mesh_from_grid(_p(d), d.shape[2], d.shape[1], d.shape[0], _p(o), float(spacing), ctypes.byref(h)),
+           "rmh_mesh_from_grid")
+    return Mesh(h)
+
+
+def mesh_extract(scene_json, **config) -> Mesh:
+    """rmh_mesh_extract: scene.json's surface D = 0 as a mesh with normals and colours; keyword
+    arguments override rmh_mesh_config's defaults (res 128, margin 0.05, smooth_k 32, radius_offset
+    0.01, refine 2, device 0)."""
+    cfg = RmhMeshConfig()
+    lib().rmh_mesh_config_default(ctypes.byref(cfg))
+    for k, v in config.items():
+        if k not in dict(RmhMeshConfig._fields_):
+            raise TypeError(f"rmh_mesh_config has no field {k!r}")
+        setattr(cfg, k, v)
+    h = _P()
+    _check(lib().rmh_mesh_extract(_b(scene_json), ctypes.byref(cfg), ctypes.byref(h)), "rmh_mesh_extract")
+    return Mesh(h)
+
+
+def mesh_write_ply(mesh: Mesh, path) -> None:
+    """rmh_mesh_write_ply: binary little-endian PLY (x y z nx ny nz float, red green blue uchar
+    sRGB-encoded, faces uchar 3 + three int)."""
+    _check(lib().rmh_mesh_write_ply(mesh.h, _b(path)), "rmh_mesh_write_ply")

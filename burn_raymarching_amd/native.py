@@ -67,6 +67,10 @@ class RmViewParams(ctypes.Structure):
 RM_VIEW_COUNT_ITERATIONS = 65536
 
 
+class RmSdfParams(ctypes.Structure):
+    _fields_ = [("smooth_k", _F), ("color_sharpness", _F), ("flags", _I32)]
+
+
 class RmGrads(ctypes.Structure):
     _fields_ = [("centers", _P), ("colors", _P), ("radius", _P), ("light_dir", _P), ("ambient", _P)]
 
@@ -104,6 +108,10 @@ SIGNATURES = {
     "rm_view_params_default": (None, [ctypes.POINTER(RmViewParams)]),
     "rm_view": (ctypes.c_int, [_P, ctypes.POINTER(RmViewCamera), _I32, _I32, _I32, ctypes.POINTER(RmScene),
                                ctypes.POINTER(RmViewParams), _P, _P, _P]),
+    "rm_sdf_params_default": (None, [ctypes.POINTER(RmSdfParams)]),
+    "rm_sdf_query": (ctypes.c_int, [_P, _P, _I64, ctypes.POINTER(RmScene), ctypes.POINTER(RmSdfParams), _P, _P, _P]),
+    "rm_sdf_grid": (ctypes.c_int, [_P, ctypes.POINTER(_F * 3), _F, _I32, _I32, _I32, ctypes.POINTER(RmScene),
+                                   ctypes.POINTER(RmSdfParams), _P, _P]),
     "rm_gather_rays": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P]),
     "rm_sample_batch": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _I64, _I64, ctypes.c_uint64, ctypes.c_uint64,
                                        ctypes.c_uint64, _P, _P, _P, _P]),
@@ -280,6 +288,18 @@ def view_params(**kw) -> RmViewParams:
     for k, v in kw.items():
         if k not in dict(RmViewParams._fields_):
             raise TypeError(f"rm_view_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def sdf_params(**kw) -> RmSdfParams:
+    """rm_sdf_params with rm_sdf_params_default's values (k = 32, colour sharpness 10, no flags);
+    keyword arguments override fields."""
+    p = RmSdfParams()
+    lib().rm_sdf_params_default(ctypes.byref(p))
+    for k, v in kw.items():
+        if k not in dict(RmSdfParams._fields_):
+            raise TypeError(f"rm_sdf_params has no field {k!r}")
         setattr(p, k, v)
     return p
 

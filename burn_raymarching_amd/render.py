@@ -13,7 +13,10 @@ Names and argument meaning follow the reference:
   * ``create_camera_rays(width, height, eye, target, fov_deg)`` -- host ray
     generation (camera.rs:30-90, a host loop in the reference too);
   * ``view(cams, width, height, scene)`` / ``view_camera(pos, yaw, pitch)`` -- the reference
-    viewer's frames (viewer.rs + shader.wgsl), headless: rm_view, not differentiable.
+    viewer's frames (viewer.rs + shader.wgsl), headless: rm_view, not differentiable;
+  * ``sdf_query(points, scene)`` / ``sdf_grid(origin, spacing, shape, scene)`` -- the scene's
+    distance field (scene.rs:60-79), its gradient and blended colour at points of the caller's
+    choosing or on a lattice: rm_sdf_query / rm_sdf_grid.
 
 Tensors are torch CUDA (HIP) tensors, fp32, ``[N, 3]``; torch provides device memory
 and the stream only. Shapes are checked on the host before any launch.
@@ -537,3 +540,41 @@ def view(cams, width, height, scene: Scene, *, params=None, rgba8=False, depth=F
                                    _ptr(dp[i:j]) if dp is not None else None), "rm_view")
     out = (rgb,) + ((px,) if rgba8 else ()) + ((dp,) if depth else ())
     return out[0] if len(out) == 1 else out
+
+
+def sdf_query(points, scene: Scene, smooth_k=32.0, *, color_sharpness=10.0, grad=True, color=True):
+    """The scene's distance field at `points` [N, 3] (rm_sdf_query): the soft-min distance D [N] of
+    scene.rs:60-79, then, if asked for, its gradient [N, 3] (sum_j softmax(-k d)_j (p - c_j) / rho_j,
+    no term from a sphere whose centre the point sits on) and the blended colour [N, 3]
+    (softmax(-color_sharpness d) over the spheres' colours, renderer_diff.rs:64-80). `scene` is used
+    as given: add the training activation's 0.01 to scene.json's radii for the surface training
+    fitted. No autograd."""
+    n = points.shape[0]
+    points = _f32(points, (n, 3), "points")
+    dev = points.device
+    dist = torch.empty((n,), device=dev)
+    g = torch.empty((n, 3), device=dev) if grad else None
+    col = torch.empty((n, 3), device=dev) if color else None
+    p = native.sdf_params(smooth_k=float(smooth_k), color_sharpness=float(color_sharpness), flags=scene.march_flags)
+    ctx = context(dev)
+    ctx.check(ctx._lib.rm_sdf_query(ctx.handle, _ptr(points), n, ctypes.byref(scene.c_struct()), ctypes.byref(p),
+                                    _ptr(dist), _ptr(g), _ptr(col)), "rm_sdf_query")
+    out = (dist,) + ((g,) if grad else ()) + ((col,) if color else ())
+    return out[0] if len(out) == 1 else out
+
+
+def sdf_grid(origin, spacing, shape, scene: Scene, smooth_k=32.0, *, color_sharpness=10.0, color=False):
+    """The distance field on a lattice (rm_sdf_grid): shape = (nx, ny, nz) points at origin +
+    float32(i) * spacing per axis, formed in the kernel in fp32 with exactly those two roundings.
+    Returns D as [nz, ny, nx] (x fastest) and, with color=True, the blended colour [nz, ny, nx, 3]."""
+    nx, ny, nz = (int(v) for v in shape)
+    dev = scene.centers.device
+    dist = torch.empty((nz, ny, nx), device=dev)
+    col = torch.empty((nz, ny, nx, 3), device=dev) if color else None
+    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
+    p = native.sdf_params(smooth_k=float(smooth_k), color_sharpness=float(color_sharpness), flags=scene.march_flags)
+    ctx = context(dev)
+    ctx.check(ctx._lib.rm_sdf_grid(ctx.handle, ctypes.byref(org), float(spacing), nx, ny, nz,
+                                   ctypes.byref(scene.c_struct()), ctypes.byref(p), _ptr(dist), _ptr(col)),
+              "rm_sdf_grid")
+    return (dist, col) if color else dist

@@ -348,6 +348,39 @@ int rm_view(rm_context* ctx, const rm_view_camera* cams, int32_t num_frames, int
             const rm_scene* scene, const rm_view_params* params, float* out_rgb, uint8_t* out_rgba8,
             float* out_depth);
 
+/* ---- the scene's distance field at points of the caller's choosing: scene.rs:60-79 --------- */
+/* What every kernel here evaluates, as a query: for a point p, with d_j = sqrt(max(|p - c_j|^2,
+ * 1e-6)) - r_j,
+ *   dist   D(p) = softmin_k(d), the log-sum-exp shifted by its maximum with the reference's
+ *          clamp_min(sum, 1e-8) (sdf.rs:30-44); finite however far p lies from the scene;
+ *   grad   grad D(p) = sum_j beta_j (p - c_j) / rho_j, beta = softmax(-k d); a sphere with
+ *          |p - c_j|^2 < 1e-6 contributes no term (the zero Jacobian of clamp_min: what autograd of
+ *          the reference's graph gives);
+ *   color  sum_j w_j col_j, w = softmax(-color_sharpness d), the blend of renderer_diff.rs:64-80.
+ * |p - c_j|^2 comes from p - c_j in direct form; the reference's expansion form differs in rounding.
+ * scene is used as given (light_dir and ambient are not read and may be NULL); whether the radii
+ * carry the +0.01 of the training activation is the caller's business. flags takes
+ * RM_MARCH_COLOR_F16 only. One dedicated kernel, one point per lane, no atomics: two identical
+ * calls give identical bits, and an output has the same bits whichever others are requested. */
+typedef struct rm_sdf_params {
+  float smooth_k;         /* soft-min sharpness k (32): finite and > 0                  */
+  float color_sharpness;  /* softmax(-c d) colour blend (10): finite and >= 0           */
+  int32_t flags;          /* RM_MARCH_COLOR_F16 or 0                                    */
+} rm_sdf_params;
+void rm_sdf_params_default(rm_sdf_params* params);   /* 32, 10, 0 */
+/* points [N,3] (device). Outputs (device pointers, any may be NULL but not all three): dist [N],
+ * grad [N,3], color [N,3]. num_points == 0 returns RM_OK without a launch. params NULL = the
+ * defaults. */
+int rm_sdf_query(rm_context* ctx, const float* points, int64_t num_points, const rm_scene* scene,
+                 const rm_sdf_params* params, float* dist, float* grad, float* color);
+/* The same on the lattice p = origin + (float)i * spacing per axis (formed in the kernel in fp32
+ * with these two roundings, no fused multiply-add, so a host reproduces the points bit for bit; no
+ * point array): origin is HOST memory, spacing > 0, nx, ny, nz >= 1. dist [nz,ny,nx] and color
+ * [nz,ny,nx,3] (either NULL, not both), x fastest: index (iz ny + iy) nx + ix. Bit for bit
+ * rm_sdf_query at those points. */
+int rm_sdf_grid(rm_context* ctx, const float origin[3], float spacing, int32_t nx, int32_t ny, int32_t nz,
+                const rm_scene* scene, const rm_sdf_params* params, float* dist, float* color);
+
 /* ---- batch gather: SceneDataset::sample_batch, dataset.rs:75-79 ---------------- */
 /* out_*[i] = src[indices[i]] for the ray origin, direction and target arrays ([num_src,3]
  * each; any output may be NULL to skip it). indices is a device int32 [num_rays]; an index

@@ -39,7 +39,7 @@ extern "C" {
 const char* rmh_last_error(void);
 void rmh_free(void* p);
 /* "burn_raymarching_amd host 0.1.0 src <16 hex>": the sha256 prefix of the host library's sources
- * (csrc/host/{io,data,driver,comm}.cpp, rmh_common.hpp, rm_host.h, raymarch.h), compiled in by
+ * (csrc/host/{io,data,driver,comm,mesh}.cpp, rmh_common.hpp, rm_host.h, raymarch.h), compiled in by
  * _build.py, so that a shipped librm_host.so names the tree it came from (rm_version() does the
  * same for libraymarch_hip.so). */
 const char* rmh_version(void);
@@ -260,6 +260,61 @@ int rmh_view(const char* scene_json, const char* out_pattern, int32_t width, int
 int rmh_png_write_rgba(const char* path, const uint8_t* rgba, int32_t width, int32_t height);
 /* 8-bit PNG -> RGBA8 [h][w][4] (alpha 255 where the file has none). */
 int rmh_png_read_rgba(const char* path, int32_t* width, int32_t* height, uint8_t** rgba);
+
+/* ---- the trained surface as a coloured triangle mesh ----------------------------------------- */
+/* The scene's soft-min D (rm_sdf_grid / rm_sdf_query, raymarch.h) is an implicit surface; these
+ * entry points turn its zero set into a mesh other tools open. The reference has no such export. */
+typedef struct rmh_mesh rmh_mesh;
+/* Marching tetrahedra on a lattice of distances (CPU only, no GPU call). dist: host [nz][ny][nx],
+ * x fastest, the layout rm_sdf_grid writes; lattice point (ix, iy, iz) lies at origin + (float)i *
+ * spacing per axis and is inside where D < 0. Every cube is cut into the same six tetrahedra (the
+ * Kuhn decomposition: the six monotone lattice paths from corner 000 to corner 111), so
+ * neighbouring cubes agree on their shared face diagonals and the surface is closed by
+ * construction. One vertex per crossing lattice edge (axis edges, face and body diagonals), shared
+ * through an edge key and placed at t = D_a / (D_a - D_b); triangles are wound so that the normal
+ * points from inside to outside. The order is fixed -- cubes z, y, x, the six tetrahedra in a
+ * fixed order, vertices numbered at first use -- so two runs give the same bytes. The mesh has no
+ * normals or colours (rmh_mesh_normals / _colors return NULL). An all-inside or all-outside grid
+ * gives an empty mesh and RMH_OK. nx, ny, nz >= 2, spacing > 0. Release with rmh_mesh_free. */
+int rmh_mesh_from_grid(const float* dist, int32_t nx, int32_t ny, int32_t nz, const float origin[3], float spacing,
+                       rmh_mesh** out);
+typedef struct rmh_mesh_config {
+  int32_t res;          /* cells along the longest extent of the box (128)                          */
+  float margin;         /* the box is that of c_j +- (r_j + margin) (0.05)                           */
+  float smooth_k;       /* soft-min sharpness (32)                                                   */
+  float radius_offset;  /* added to scene.json's radii: 0.01 is the surface training fitted (0.01)   */
+  int32_t refine;       /* Newton projections v -= D g / |g|^2 of the vertices onto D = 0 (2)        */
+  int32_t device;
+} rmh_mesh_config;
+void rmh_mesh_config_default(rmh_mesh_config* cfg);
+/* scene.json -> mesh: loads the scene (radii + radius_offset), takes the axis-aligned box of
+ * c_j +- (r_j + margin) with cubic cells of (longest extent / res), evaluates D on its lattice with
+ * rm_sdf_grid, copies the grid to the host and extracts (rmh_mesh_from_grid); then `refine` Newton
+ * projections of the vertices through rm_sdf_query (a vertex with |g|^2 < 1e-12 keeps its place)
+ * and one more query for the per-vertex normals g / |g| and the blended colours. cfg NULL = the
+ * defaults. */
+int rmh_mesh_extract(const char* scene_json, const rmh_mesh_config* cfg, rmh_mesh** out);
+/* open_edges: the undirected edges that do not lie in exactly two triangles -- non-zero only where
+ * the surface leaves the grid. The soft-min surface lies outside the spheres where they blend, by at
+ * most ln(M) / k (D >= min_j d_j - ln(M) / k): a margin of that much always closes the mesh; the
+ * default 0.05 does for scenes of a few spheres per neighbourhood (the grown 4096-sphere model
+ * needs more). */
+void rmh_mesh_counts(const rmh_mesh* mesh, int64_t* vertices, int64_t* faces, int64_t* open_edges);
+/* Host arrays owned by the mesh: vertices [V][3], normals [V][3] (unit) and colours [V][3] (linear
+ * RGB in [0, 1]; both NULL for a mesh of rmh_mesh_from_grid), faces [F][3] vertex indices. */
+const float* rmh_mesh_vertices(const rmh_mesh* mesh);
+const float* rmh_mesh_normals(const rmh_mesh* mesh);
+const float* rmh_mesh_colors(const rmh_mesh* mesh);
+const int32_t* rmh_mesh_faces(const rmh_mesh* mesh);
+/* Milliseconds rmh_mesh_extract spent: ms[0] the grid evaluation, [1] its copy to the host, [2] the
+ * extraction, [3] the refinement and the final query (zeros for a mesh of rmh_mesh_from_grid). */
+void rmh_mesh_timing(const rmh_mesh* mesh, double ms[4]);
+void rmh_mesh_free(rmh_mesh* mesh);
+/* Binary little-endian PLY: per vertex x y z nx ny nz (float) and red green blue (uchar: the
+ * piecewise sRGB encode of rm_view's RGBA8 output, rounded to nearest), per face uchar 3 + three
+ * int -- 27 V + 13 F bytes after the header. A mesh without normals / colours writes zero normals
+ * and white. Creates missing parent directories. */
+int rmh_mesh_write_ply(const rmh_mesh* mesh, const char* path);
 
 /* ---- generate.rs:20-112: target images + cameras.json ---------------------------------- */
 /* Renders the three-sphere scene from the 10 generate.rs cameras with rm_render_camera and
