@@ -313,6 +313,9 @@ int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres) {
     const int np = pad_spheres(max_spheres) / 2;
     if ((rc = ctx->rec.ensure(ctx, rec_bytes(np, (np + 255) / 256), "record buffer")) != RM_OK) return rc;
   }
+  if (rays >= kLatticeMinRays && pad_spheres(max_spheres) >= kProofMinSpheres &&
+      (rc = ctx->lattice.ensure(ctx, sizeof(float) * kLatticeCells, "escape lattice")) != RM_OK)
+    return rc;
   return ctx->ws.ensure(ctx, ws_need(rays, max_spheres), "workspace");
 }
 

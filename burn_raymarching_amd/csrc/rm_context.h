@@ -53,6 +53,7 @@ struct rm_context {
   DevBuf cont_buf;      // split continuation: saved march state | list | count
   DevBuf stats_dev;     // work counters (rm_stats_enable), kStatsWords words
   DevBuf esc_flags;     // per-block escape flags, kMaxBlocksPerLaunch ints
+  DevBuf lattice;       // the current call's escape lattice, kLatticeN^3 floats (rm_lattice_kernel)
   DevBuf arrivals;      // rm_small_kernel's arrival counter (zero between launches)
   DevBuf red_arrivals;  // rm_reduce_partials' per-column-block arrival counters
   DevBuf opt_arrival;   // rm_train_step_camera_adam: the reduction's column-block counter

@@ -104,7 +104,8 @@ struct KArgs {
                               // backward sweeps run for (non-zero seeds)
   float gone_d;               // > 0: rays that provably escape past this distance are `gone` (see the march)
   int early_exit;             // waves whose rays are all gone stop marching
-  int proof;                  // the escape proof before the march (rm_ray_kernel<.., PROOF>; march_policy)
+  int proof;                  // the escape proof before the march (rm_ray_kernel<.., PROOF>; march_policy): 1 the
+                              // soft ball alone, 2 with the call's lattice
   int split;                  // split march (RM_MARCH_SPLIT): 64 rays per block, a quarter of the spheres per wave
   int mfma;                   // march sums on the matrix cores (lse_mfma) instead of lse_weighted
   int shift_max;              // RM_MARCH_FORCE_MAX_SHIFT: every march step takes the running-max shift
@@ -179,6 +180,9 @@ struct KArgs {
   const int* ray_count;
   int* ray_list_w;
   int* ray_count_w;
+  // nullable: the call's escape lattice, kLatticeN^3 cell-centre soft-min values (proof == 2;
+  // rm_lattice_kernel). Last, so that the kernels that never read it see the arguments where they were.
+  const float* lattice;
 #ifdef RM_BLOCK_TRACE
   unsigned long long* btrace;  // measurement build: per-wave timing records (rm_ray_kernel)
 #endif
@@ -234,8 +238,15 @@ __host__ __device__ inline size_t esc_offset(int npairs, int nprep) {
 __host__ __device__ inline size_t origin_offset(int npairs, int nprep) {
   return esc_offset(npairs, nprep) + kEscTab * sizeof(float);
 }
-__host__ __device__ inline size_t rec_bytes(int npairs, int nprep) {
+// Then the geometry of the call's escape lattice (write_bound; bound_proof in rm_ray_kernel), kLatGeom
+// floats: {x, y, z of cell centre 0, h, half-side, 1 / h, slack, 0}. It depends on the scene's bounding
+// sphere, which only the record kernel knows, so it lives here and not in KArgs.
+constexpr int kLatGeom = 8;
+__host__ __device__ inline size_t lattice_offset(int npairs, int nprep) {
   return origin_offset(npairs, nprep) + 2 * RM_MAX_VIEWS_PER_CALL * sizeof(float);
+}
+__host__ __device__ inline size_t rec_bytes(int npairs, int nprep) {
+  return lattice_offset(npairs, nprep) + kLatGeom * sizeof(float);
 }
 
 struct Lds {  // the sphere records (global, scalar-loaded) plus the kernel's LDS scratch
@@ -432,6 +443,13 @@ __device__ __forceinline__ bool mfma_w_fixed(int e) { return (e & 16) != 0; }
 // slower with the proof. A call without the proof (KArgs::proof, march_policy) launches the kernel
 // instance without it, and its record kernel skips the pass: hdr[3] = R + ln(M)/k, the ball's bound.
 constexpr int kProofMinSpheres = 128;
+// The escape lattice of the camera-mode proof (bound_proof; KArgs::lattice): kLatticeN^3 cells over the cube
+// of half-side R' + kLatticeMargin about c_0. Sized by tools/escape_proof_sim.py on the bench scene after
+// 35 optimizer steps (profiles/r19_escape_lattice_sim.txt): 64 cells save 26.7 % of the march's packed
+// column blocks where the soft ball alone saves 2.9 %; 96 / 128 add 2 / 4 points for 3.4 / 8 times the fill
+// and a table of 3.5 / 8 MB against the 4 MB L2; the margin hardly matters (0.1 / 0.25 / 0.5: 27.0 / 26.7 / 25.7 %).
+constexpr int kLatticeN = 64;
+constexpr float kLatticeMargin = 0.25f;
 __device__ __forceinline__ float soft_radius(const KArgs& a, float* scratch, int tid, const float c0[3], float R) {
   const int lane = tid & 63, wave = tid >> 6, nt = (int)blockDim.x, nw = nt >> 6;
   const float kappa = a.k * kLog2e;
@@ -473,6 +491,21 @@ __device__ void write_bound(const KArgs& a, float* hdr, float* esc) {
     hdr[5] = c[1];
     hdr[6] = c[2];
     hdr[7] = R;
+    if (a.lattice != nullptr) {
+      // The escape lattice of this call (kLatticeN; rm_lattice_kernel fills it, bound_proof reads it): the
+      // cube of half-side R' + kLatticeMargin about c_0 in kLatticeN^3 cells of side h, cell i's centre at
+      // -half + (i + 0.5) h per axis. The division is done here, once: the ray kernel multiplies by 1 / h.
+      // slack: see bound_proof.
+      float* lat = esc + kEscTab + 2 * RM_MAX_VIEWS_PER_CALL;
+      const float half = (R + a.lse_slack + 1e-3f) * (1.0f + 1e-6f) + kLatticeMargin;
+      const float h = 2.0f * half / (float)kLatticeN;
+      for (int k = 0; k < 3; ++k) lat[k] = (c[k] - half) + 0.5f * h;
+      lat[3] = h;
+      lat[4] = half;
+      lat[5] = 1.0f / h;
+      lat[6] = h * (0.8660254f * (1.0f + 1e-4f)) + 1e-3f;
+      lat[7] = 0.0f;
+    }
   }
   if (threadIdx.x < kEscTab) {
     // f32 with a 1e-5 relative + 1e-6 absolute round-up per iteration (the f32 rounding of one

@@ -398,6 +398,29 @@ int prepare_records(rm_context* ctx, KArgs& a, bool origin) {
   return RM_OK;
 }
 
+// The call's escape lattice (KArgs::lattice; bound_proof in rm_ray_kernel): the soft-min at the
+// kLatticeN^3 cell centres the record kernel laid out, by the distance-only lattice sweep of
+// rm_sdf_grid. Once per call, after the record kernels and before the per-ray launches, on the call's
+// stream: the scene changes with every optimizer step, so nothing of it is kept across calls.
+constexpr size_t kLatticeCells = (size_t)kLatticeN * kLatticeN * kLatticeN;
+int fill_lattice(rm_context* ctx, const KArgs& a) {
+  const int np = a.Mpad / 2;
+  SdfArgs s;
+  std::memset(&s, 0, sizeof s);
+  s.rec_buf = a.rec_buf;
+  s.Mpad = a.Mpad;
+  s.kappa = a.k * kLog2e;
+  s.n = (long long)kLatticeCells;
+  s.nx = kLatticeN;
+  s.ny = kLatticeN;
+  s.dist = const_cast<float*>(a.lattice);
+  s.geom = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.rec_buf) + lattice_offset(np, (np + 255) / 256));
+  static_assert(kLatticeCells % kBlock == 0 && kLatticeCells / kBlock <= kMaxBlocksPerLaunch, "one launch");
+  hipLaunchKernelGGL(rm_lattice_kernel, dim3((unsigned)(kLatticeCells / kBlock)), dim3(kBlock), 0, ctx->stream, s);
+  RM_HIP(ctx, hipGetLastError());
+  return RM_OK;
+}
+
 // ---- the gradient reduction ------------------------------------------------------------------
 
 FinalArgs final_args(const Call& c, bool first) {
@@ -644,6 +667,13 @@ int check_call(rm_context* ctx, const Call& c, long long n) {
   return RM_OK;
 }
 
+// The escape lattice costs a call one rm_lattice_kernel launch (kLatticeN^3 M evaluations, about 24 us at
+// 256 spheres) whatever its size, and saves in proportion to its rays. Measured on the bench scene, 512x512
+// views of 256 spheres, lattice against soft ball alone (profiles/r19_escape_lattice_ab.txt): 80 views
+// +12.7 %, 10 views +10 %, 4 views +4.5 %, 2 views -1 % (inside the noise), 1 view -5 %, a 256x256 view
+// -11 %. Camera calls below kLatticeMinRays rays (4 views of 512x512) keep the soft ball alone.
+constexpr long long kLatticeMinRays = 1048576;
+
 // How the call marches, into KArgs: the split march, the escape pre-pass, the early exit and the
 // flags that select march paths. Returns whether the call takes the split march.
 bool march_policy(const Call& c, long long n, KArgs& a) {
@@ -680,6 +710,11 @@ bool march_policy(const Call& c, long long n, KArgs& a) {
   // the escape proof (rm_ray.h, bound_proof): the unsplit training kernels with the exit on (hence no
   // per-ray t and no debug output), from kProofMinSpheres spheres on
   a.proof = a.early_exit && !split && c.mode != kRender && a.Mpad >= kProofMinSpheres ? 1 : 0;
+  // with the call's escape lattice (proof = 2; run() fills it): camera calls of at least kLatticeMinRays
+  // rays; env RM_PROOF_LATTICE=0 never, =1 at any size (read per call, as RM_SPLIT). Other calls keep the
+  // soft ball alone.
+  if (a.proof && c.cam && !env_is("RM_PROOF_LATTICE", '0') && (n >= kLatticeMinRays || env_is("RM_PROOF_LATTICE", '1')))
+    a.proof = 2;
   a.mfma = (c.march->flags & RM_MARCH_VALU_ONLY) == 0;
   a.shift_max = (c.march->flags & RM_MARCH_FORCE_MAX_SHIFT) != 0;
   if (c.mode == kRender) {  // renderer.rs:27-32, normalised in f32 on the host like the reference
@@ -905,7 +940,12 @@ int run(rm_context* ctx, const Call& c) {
   if (use_small(c, a.M, n)) return run_small(ctx, c, a, n);
   if (c.fused) return fail(ctx, RM_ERR_INVALID_ARG, "fused iteration outside the small kernel");
   const bool origin = c.cam && (c.march->flags & (RM_MARCH_PER_RAY_ORIGIN | RM_MARCH_FORCE_MAX_SHIFT)) == 0;
+  if (a.proof == 2 && n > 0) {  // set before the record kernel, which lays the lattice out (write_bound)
+    if ((rc = ctx->lattice.ensure(ctx, sizeof(float) * kLatticeCells, "escape lattice")) != RM_OK) return rc;
+    a.lattice = ctx->lattice.as<float>();
+  }
   if (n > 0 && (rc = prepare_records(ctx, a, origin)) != RM_OK) return rc;
+  if (a.lattice != nullptr && (rc = fill_lattice(ctx, a)) != RM_OK) return rc;
 
   const int rpb = split ? kSplitRays : kBlock;  // rays per block
   if (has_bwd && (rc = ctx->ws.ensure(ctx, ws_need(std::max<long long>(n, 1), a.M, rpb), "workspace")) != RM_OK)

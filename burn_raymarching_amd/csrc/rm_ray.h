@@ -550,12 +550,39 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // below 256 x 6e-8 each, 1e-4 in all. A wave gives up once a ray's bound step falls to
     // kProofMinStep (not to 0: a ray creeping along the ball is not proven in the steps left either,
     // tools/escape_proof_sim.py): what the proof tries changes no result.
+    // Camera mode with the call's lattice (KArgs::lattice, march_policy): L = max(|p - c_0| - R_soft, G[cell] - slack)
+    // inside the lattice's cube, the soft ball alone outside it. G[cell] is the soft-min at the cell's centre
+    // x_c (rm_lattice_kernel) and D is 1-Lipschitz, so D(p) >= D(x_c) - |p - x_c|: a point of the cell is at
+    // most the half-diagonal h sqrt(3)/2 from x_c. The soft ball needs spheres out of the way in every
+    // direction; the lattice sees the gaps between them (once the optimizer has thrown a few spheres
+    // outwards, R_soft covers all the rays thread through: profiles/r19_escape_lattice_sim.txt).
+    // Margins: slack = h sqrt(3)/2 (1 + 1e-4) + 1e-3 (write_bound), and the two 1e-3 of the soft ball on top (the
+    // march's and the bound step's). The 1e-4 relative covers the cell index: (e + half) / h is formed with
+    // three roundings, below 3e-7 N cells in all, so a point rounded into a neighbouring cell is within
+    // (1/2 + 2e-5) h of that cell's centre per axis. The 1e-3 covers the lattice kernel's fp32: its cell
+    // centres origin + i h (three roundings at magnitude <= B: 5e-5 per axis), its direct-form distances
+    // (one rounding of e at magnitude <= B, 3e-5; the square root and the sum 1e-6 relative of a distance
+    // below 2 B) and its logarithm (1e-6 / kappa). The maximum of two lower bounds is a lower bound; the
+    // give-up rule, the votes and steps_saved are the soft ball's. Array mode keeps the soft ball alone.
+    static_assert((kLatticeN & (kLatticeN - 1)) == 0, "the inside test takes a power of two");
     constexpr float kProofMinStep = 0.02f;
     auto bound_proof = [&](int st) {
       // a wave vote: origins differ per lane (array mode; a wave across two views), and every lane
       // takes part in the votes below and must leave with the same answer (dead is wave-uniform)
       if (__any(!(onorm + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= 256.0f))) return false;
       const float rs = (hdr[3] + 1e-3f) * (1.0f + 1e-6f) + 1e-3f;
+      // the lattice's geometry (write_bound): half-side, 1 / h and the slack with the two 1e-3 of rs on top
+      const bool lat = CAM && a.lattice != nullptr;
+      float lat_half = 0.0f, lat_inv_h = 0.0f, lat_slack = 0.0f;
+      if constexpr (CAM) {
+        if (lat) {
+          const cf1_ptr lg = (cf1_ptr)(reinterpret_cast<const char*>(a.rec_buf) +
+                                       lattice_offset(a.Mpad / 2, (a.Mpad / 2 + 255) / 256));
+          lat_half = lg[4];
+          lat_inv_h = lg[5];
+          lat_slack = lg[6] + 2e-3f;
+        }
+      }
       float u = t;
       bool proven = gone || !valid;
       for (int n = st; n < a.steps; ++n) {
@@ -567,7 +594,23 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
           steps_saved += a.steps - st;
           return true;
         }
-        const float Lb = dist - rs;
+        float Lb = dist - rs;
+        if constexpr (CAM) {
+          if (lat) {
+            // the cell per axis, floor((e + half) / h), from a coordinate held to [-1, N] (no conversion out
+            // of range); inside the cube is decided on the integers, and a lane outside reads a clamped
+            // cell whose value the select drops: one load per lane, no branch per lane
+            constexpr float kN = (float)kLatticeN;
+            const int ix = (int)__builtin_floorf(__builtin_amdgcn_fmed3f((ex + lat_half) * lat_inv_h, -1.0f, kN));
+            const int iy = (int)__builtin_floorf(__builtin_amdgcn_fmed3f((ey + lat_half) * lat_inv_h, -1.0f, kN));
+            const int iz = (int)__builtin_floorf(__builtin_amdgcn_fmed3f((ez + lat_half) * lat_inv_h, -1.0f, kN));
+            const bool inside = (unsigned)(ix | iy | iz) < (unsigned)kLatticeN;
+            const int cx = min(max(ix, 0), kLatticeN - 1), cy = min(max(iy, 0), kLatticeN - 1),
+                      cz = min(max(iz, 0), kLatticeN - 1);
+            const float g = a.lattice[(cz * kLatticeN + cy) * kLatticeN + cx];
+            Lb = fmaxf(Lb, inside ? g - lat_slack : -INFINITY);
+          }
+        }
         if (__any(!proven && !(Lb > kProofMinStep))) return false;
         u += proven ? 0.0f : Lb;
       }

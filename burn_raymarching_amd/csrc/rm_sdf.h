@@ -36,6 +36,7 @@ struct SdfArgs {
   float* dist;   // nullable [n]
   float* grad;   // nullable [n,3]
   float* color;  // nullable [n,3]
+  const float* geom;  // rm_lattice_kernel: {origin x, y, z, spacing} in device memory (origin / spacing unused)
 };
 
 template <bool FULL>
@@ -113,8 +114,10 @@ __device__ __forceinline__ void sdf_sweep(const float p[3], const Lds& L, int np
   }
 }
 
-template <bool GRID, bool FULL>
-__global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_sdf_kernel(const SdfArgs a) {
+// DEV: the lattice's origin and spacing come from device memory (a.geom: {x, y, z, spacing}) instead of
+// the arguments -- the escape lattice's, which the record kernel forms (write_bound).
+template <bool GRID, bool FULL, bool DEV>
+__device__ __forceinline__ void sdf_body(const SdfArgs& a) {
   Lds L;
   const int np = a.Mpad / 2;
   L.P0 = (cf4_ptr)a.rec_buf;
@@ -139,9 +142,17 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_sdf_kernel(const 
       const long long row = idx / a.nx;
       const int ix = (int)(idx - row * a.nx);
       const int iz = (int)(row / a.ny), iy = (int)(row - (long long)iz * a.ny);
-      p[0] = a.origin[0] + (float)ix * a.spacing;
-      p[1] = a.origin[1] + (float)iy * a.spacing;
-      p[2] = a.origin[2] + (float)iz * a.spacing;
+      if constexpr (DEV) {
+        const cf1_ptr g = (cf1_ptr)a.geom;
+        const float h = g[3];
+        p[0] = g[0] + (float)ix * h;
+        p[1] = g[1] + (float)iy * h;
+        p[2] = g[2] + (float)iz * h;
+      } else {
+        p[0] = a.origin[0] + (float)ix * a.spacing;
+        p[1] = a.origin[1] + (float)iy * a.spacing;
+        p[2] = a.origin[2] + (float)iz * a.spacing;
+      }
     } else {
       p[0] = a.points[3 * idx];
       p[1] = a.points[3 * idx + 1];
@@ -166,4 +177,15 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_sdf_kernel(const 
       a.color[3 * idx + 2] = col[2] * iz;
     }
   }
+}
+
+template <bool GRID, bool FULL>
+__global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_sdf_kernel(const SdfArgs a) {
+  sdf_body<GRID, FULL, false>(a);
+}
+
+// The escape lattice of a call (KArgs::lattice; bound_proof in rm_ray_kernel): the distance-only lattice
+// sweep above, bit for bit, at the cell centres write_bound laid out for this call's scene.
+__global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_lattice_kernel(const SdfArgs a) {
+  sdf_body<true, false, true>(a);
 }

@@ -1,0 +1,190 @@
+"""The escape lattice of the camera-mode escape proof (bound_proof in rm_ray.h,
+rm_lattice_kernel): the bound march steps by the larger of the soft ball and the call's lattice of
+cell-centre soft-min values. Exact: the train step with the lattice, with the soft ball alone
+(RM_PROOF_LATTICE=0) and with the exit off (RM_NO_EARLY_EXIT=1) gives the same bits, and the rm_stats
+counters show what the lattice adds. The calls here are far below kLatticeMinRays, so the lattice is
+switched on by RM_PROOF_LATTICE=1 (the policy test leaves it unset). RM_SMALL=0 / RM_SPLIT=0: the
+general unsplit kernel, the proof's scope."""
+import numpy as np
+import pytest
+
+from conftest import gpu_available
+from test_escape_lattice_reference import (GAP_CAM, Geometry, cloud_scene, coincident_scene, gap_scene, outlier_scene,
+                                           wave_tiles)
+
+pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
+
+
+@pytest.fixture(scope="module")
+def mods():
+    import torch
+    from burn_raymarching_amd import model, native, render
+    torch.cuda.init()
+    return torch, model, render, native
+
+
+@pytest.fixture(autouse=True)
+def general_kernel(monkeypatch):
+    monkeypatch.setenv("RM_SMALL", "0")
+    monkeypatch.setenv("RM_SPLIT", "0")
+    monkeypatch.delenv("RM_PROOF_LATTICE", raising=False)
+    monkeypatch.delenv("RM_NO_EARLY_EXIT", raising=False)
+
+
+def _plane_cams(sc, k):
+    """eye and target on a cell face of the lattice (y = a lattice plane): the central ray runs along it"""
+    g = Geometry(sc, k)
+    y = g.c0[1] - g.half + 40 * g.h
+    return [([g.c0[0] + 0.3, y, g.c0[2] + 2.5], [g.c0[0] - 0.5, y, g.c0[2]], 50.0)]
+
+
+FAR = np.array([29.0, -29.0, 29.0])  # 50.2 from the origin
+
+# name: (scene, cameras, (w, h), march steps, k)
+CASES = {
+    "beside": lambda: (cloud_scene(300), [([0.0, 0.5, 2.5], [2.2, 0.5, 0.0], 20.0)], (48, 80), 32, 32.0),
+    "gap": lambda: (gap_scene(128), [GAP_CAM], (48, 80), 32, 32.0),
+    "gap-two-views": lambda: (gap_scene(128), [GAP_CAM, ([0.3, 0.2, -2.6], [0.0, 0.0, 0.0], 30.0)], (64, 64), 32, 32.0),
+    "in-cube-outside-cloud": lambda: (cloud_scene(300), [([0.9, 0.35, 0.3], [0.0, 1.6, 0.0], 70.0)], (64, 64), 32, 32.0),
+    "inside-cloud": lambda: (cloud_scene(300), [([0.05, 0.0, -0.1], [1.0, 0.3, 0.2], 70.0)], (48, 80), 32, 32.0),
+    "far-from-origin": lambda: (cloud_scene(128, centre=FAR), [(list(FAR + [0.0, 0.5, 2.5]), list(FAR + [1.6, 0.5, 0.0]), 40.0)],
+                                (64, 64), 8, 32.0),
+    "one-centre": lambda: (coincident_scene(128), [([0.0, 0.3, 2.0], [0.6, 0.0, 0.0], 60.0)], (48, 80), 8, 5.0),
+    "outliers-k5": lambda: (outlier_scene(300), [([0.0, 0.5, 3.5], [2.0, 0.5, 0.0], 40.0)], (64, 64), 32, 5.0),
+    "lattice-plane": lambda: (outlier_scene(128), _plane_cams(outlier_scene(128), 32.0), (64, 64), 32, 32.0),
+}
+
+
+def _train(mods, sc, cams, w, h, S, k):
+    torch, _, render, _ = mods
+    tgt = torch.full((len(cams) * w * h, 3), 0.25, device="cuda")
+    out = torch.empty_like(tgt)
+    ctx = render.context()
+    ctx.stats(True)
+    ctx.collect_stats(reset=True)
+    loss, g, _ = render.train_step_camera(cams, w, h, tgt, sc, k, 0.5, S, out=out)
+    torch.cuda.synchronize()
+    st = ctx.collect_stats(reset=True)
+    ctx.stats(False)
+    return dict(loss=loss.clone(), out=out.clone(), **{key: v.clone() for key, v in g.items()}), st
+
+
+@pytest.fixture(scope="module")
+def runs(mods):
+    """per case, computed once: the train step and its counters with the lattice, with the soft ball alone and
+    with the exit off"""
+    cache = {}
+
+    def get(name, monkeypatch):
+        if name not in cache:
+            torch, model, _, _ = mods
+            scd, cams, (w, h), S, k = CASES[name]()
+            sc = model.scene_tensors(scd, "cuda")
+            res = {}
+            for mode, env in (("lattice", {"RM_PROOF_LATTICE": "1"}), ("ball", {"RM_PROOF_LATTICE": "0"}),
+                              ("exit-off", {"RM_NO_EARLY_EXIT": "1", "RM_PROOF_LATTICE": "1"})):
+                with monkeypatch.context() as mp:
+                    for key, v in env.items():
+                        mp.setenv(key, v)
+                    res[mode] = _train(mods, sc, cams, w, h, S, k)
+            cache[name] = (res, len(cams), w, h, S)
+        return cache[name]
+    return get
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_lattice_changes_no_bit_and_saves_no_less(mods, runs, monkeypatch, name):
+    torch = mods[0]
+    res, views, w, h, S = runs(name, monkeypatch)
+    (lat, st_lat), (ball, st_ball), (off, st_off) = res["lattice"], res["ball"], res["exit-off"]
+    for key in lat:
+        assert torch.equal(lat[key], ball[key]) and torch.equal(lat[key], off[key]), key
+        assert bool(torch.isfinite(lat[key]).all()), key
+    print(name, "lattice", st_lat, "ball", st_ball)
+    assert st_lat["waves"] == st_ball["waves"] == st_off["waves"] == views * w * h // 64
+    assert st_lat["steps_saved"] >= st_ball["steps_saved"]
+    assert st_lat["waves_exited"] >= st_ball["waves_exited"]
+    assert st_off["waves_exited"] == 0
+
+
+@pytest.mark.parametrize("name", ["gap", "gap-two-views"])
+def test_gap_scene_saves_more_and_exits_no_wave_that_shows(mods, runs, monkeypatch, name):
+    res, views, w, h, S = runs(name, monkeypatch)
+    (lat, st_lat), (_, st_ball) = res["lattice"], res["ball"]
+    assert st_lat["steps_saved"] > st_ball["steps_saved"]
+    # a wave is an 8x8 pixel tile of a view; one that holds a non-zero pixel was not exited (an exited wave
+    # writes zeros: the bits equal the exit-off run's, test above), so at most the all-zero waves exited
+    shown = (lat["out"].abs().amax(1) > 0).view(views, w * h).cpu().numpy()
+    waves_shown = sum(int(shown[v][wave_tiles(w, h)].any(1).sum()) for v in range(views))
+    assert waves_shown > 0
+    assert st_lat["waves_exited"] <= st_lat["waves"] - waves_shown
+
+
+def test_inside_the_cloud_the_counters_are_the_soft_balls(mods, runs, monkeypatch):
+    res = runs("inside-cloud", monkeypatch)[0]
+    st_lat, st_ball = res["lattice"][1], res["ball"][1]
+    assert (st_lat["waves_exited"], st_lat["steps_saved"]) == (st_ball["waves_exited"], st_ball["steps_saved"])
+
+
+def test_policy_keeps_small_calls_on_the_soft_ball(mods, runs, monkeypatch):
+    """a call below kLatticeMinRays, taken through the policy with no switch set, reports the soft ball's
+    counters (and the lattice's differ on this scene, so the comparison can tell)"""
+    _, model, _, _ = mods
+    res = runs("gap", monkeypatch)[0]
+    scd, cams, (w, h), S, k = CASES["gap"]()
+    got, st = _train(mods, model.scene_tensors(scd, "cuda"), cams, w, h, S, k)
+    assert st == res["ball"][1]
+    assert st["steps_saved"] < res["lattice"][1]["steps_saved"]
+    for key in got:
+        assert mods[0].equal(got[key], res["ball"][0][key]), key
+
+
+def test_graph_replay_rebuilds_the_lattice(mods, monkeypatch):
+    """Two calls on two scenes captured in one graph and replayed twice, the scenes moved in place before
+    every run: the replays give the eager runs' bits, so each call's lattice is built inside the replay from
+    the scene as it then is. The gap scene's clusters move into the gap: a lattice kept from the capture, or
+    the other call's, would still see the gap and prove waves whose pixels now show."""
+    torch, model, render, _ = mods
+    monkeypatch.setenv("RM_PROOF_LATTICE", "1")
+    w, h, S, k = 64, 64, 32, 32.0
+    cams = [GAP_CAM]
+    s = torch.cuda.Stream()
+    results = {}
+    with torch.cuda.stream(s):
+        ctx = render.context()
+        for mode in ("eager", "graph"):
+            scenes = [model.scene_tensors(gap_scene(128), "cuda"), model.scene_tensors(outlier_scene(128), "cuda")]
+            tgt = torch.full((w * h, 3), 0.25, device="cuda")
+            bufs = [torch.zeros(model.packed_size(128) + 1, device="cuda") for _ in scenes]
+            outs = [torch.empty_like(tgt) for _ in scenes]
+
+            def step():
+                for sc, buf, out in zip(scenes, bufs, outs):
+                    render.train_step_camera(cams, w, h, tgt, sc, k, 0.5, S, grads_packed=buf[:-1], loss=buf[-1:],
+                                             out=out, ctx=ctx)
+
+            def move():  # the gap's clusters move into the gap, the outlier scene drifts: other lattices every run
+                scenes[0].centers[:, 0].mul_(0.5)
+                scenes[1].centers.add_(0.15)
+
+            step()  # every buffer allocated before the capture
+            torch.cuda.synchronize()
+            seq = []
+            if mode == "graph":
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, stream=s):
+                    step()
+            for _ in range(2):
+                move()
+                if mode == "graph":
+                    g.replay()
+                else:
+                    step()
+                seq.append([t.clone() for t in bufs + outs])
+            torch.cuda.synchronize()
+            results[mode] = seq
+    for run, (a, b) in enumerate(zip(results["eager"], results["graph"])):
+        for i, (x, y) in enumerate(zip(a, b)):
+            assert torch.equal(x, y), (run, i)
+    # the runs differ from one another: the scenes did move
+    assert not torch.equal(results["eager"][0][2], results["eager"][1][2])

@@ -21,6 +21,12 @@ Bound families:
             bounds (L(i h) + L((i + 1) h) - h) / 2 over [0, R'), the soft ball outside
   ballsK    L = -(1/k) ln sum_c n_c exp(-k (|p - C_c| - R_c)) - 1e-3, K balls over Morton-order
             runs of the spheres, R_c >= |c_j - C_c| + r_j, n_c members
+  gridN[:m] the larger of the soft ball and a lattice bound: N^3 cell-centre soft-min values (direct-form distances,
+            float32) over the cube of half-side R' + m (default 0.25) about c_0, spacing h = 2 (R' + m) / N, each less
+            h sqrt(3)/2 (1 + 1e-5) + 1e-3 -- the soft-min is 1-Lipschitz and no point of a cell is further than the
+            half-diagonal from its centre; the cell is floor((p - c_0 + half) / h) per axis, and outside the cube the
+            bound is the soft ball alone. One table read per bound step whatever N: K = 1 in the cost model, the
+            lattice build (N^3 M evaluations per call) not counted
 
 softball, radial and radtab print the same figures on the bench scenes: every proof the radial bound finds
 comes from rho past the outermost centre, where it is exactly rho - R_soft. That is the finding the kernel
@@ -99,6 +105,29 @@ def bound_fn(family, c, r, c0, rp, k):
             rho = np.sqrt(((p - c0) ** 2).sum(-1))
             cell = np.minimum((rho / h).astype(np.int64), 254)
             return np.where(rho / h < 255, np.maximum(tab[cell], rho - rs), rho - rs)
+        return L, 1
+    if family.startswith("grid"):
+        name, _, mg = family.partition(":")
+        N, margin = int(name[4:]), float(mg) if mg else 0.25
+        Ls = bound_fn("softball", c, r, c0, rp, k)[0]
+        half = F(rp + margin)
+        h = F(2) * half / F(N)
+        inv_h = F(1) / h
+        ax = -half + (np.arange(N, dtype=F) + F(0.5)) * h
+        G = np.empty((N, N, N), F)  # [iz, iy, ix]
+        gy, gx = np.meshgrid(ax, ax, indexing="ij")
+        for iz in range(N):
+            e = (c0 + np.stack([gx, gy, np.full_like(gx, ax[iz])], -1))[..., None, :] - c
+            x = -k * (np.sqrt(np.maximum((e * e).sum(-1), F(1e-6))) - r)
+            m = x.max(-1)
+            G[iz] = -(m + np.log(np.exp(x - m[..., None]).sum(-1, dtype=F))) / k
+        G -= h * F(math.sqrt(3) / 2 * (1 + 1e-5)) + F(1e-3)
+
+        def L(p):
+            i = np.floor((p - c0 + half) * inv_h)
+            inside = ((i >= 0) & (i < N)).all(-1)
+            i = np.clip(i, 0, N - 1).astype(np.int64)
+            return np.maximum(Ls(p), np.where(inside, G[i[..., 2], i[..., 1], i[..., 0]], -np.inf)).astype(F)
         return L, 1
     C, R, n = morton_balls(c, r, int(family[5:]))
     ln_n = np.log(n)
@@ -237,7 +266,7 @@ def main():
                 cost += steps_run.sum() * (K + 1) / Mpad
             res.append((done.mean(), sv_w / ws, sv_b / cb, cost / ws))
         a, b = res[0], res[-1]
-        print(f"  {family:8s}  {a[0]:.3f}          ({b[0]:.3f})    {a[1]:.3f}              ({b[1]:.3f})"
+        print(f"  {family:{max(8, len(family))}s}  {a[0]:.3f}          ({b[0]:.3f})    {a[1]:.3f}              ({b[1]:.3f})"
               f"       {a[2]:.3f}          ({b[2]:.3f})    {a[3]:.4f} ({b[3]:.4f})  {a[1] - a[3]:.3f}             ({b[1] - b[3]:.3f})")
 
 
