@@ -310,8 +310,7 @@ int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres) {
   if ((rc = ctx->opt_pre.ensure(ctx, sizeof(float) * (4 * kOptPreStride + 2), "optimizer hand-off")) != RM_OK) return rc;
   if ((rc = ctx->rg_ws.ensure(ctx, rg_need(rays), "ray-gradient workspace")) != RM_OK) return rc;
   {  // the sphere records: all the scratch rm_view takes
-    const int np = pad_spheres(max_spheres) / 2;
-    if ((rc = ctx->rec.ensure(ctx, rec_bytes(np, (np + 255) / 256), "record buffer")) != RM_OK) return rc;
+    if ((rc = ctx->rec.ensure(ctx, RecLayout(pad_spheres(max_spheres)).bytes(), "record buffer")) != RM_OK) return rc;
   }
   if (rays >= kLatticeMinRays && pad_spheres(max_spheres) >= kProofMinSpheres &&
       (rc = ctx->lattice.ensure(ctx, sizeof(float) * kLatticeCells, "escape lattice")) != RM_OK)

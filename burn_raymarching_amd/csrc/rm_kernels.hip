@@ -16,7 +16,7 @@
 //   [train] weighted-L1 seed              (training.rs:17-34)
 //   [bwd]   analytic backward: sweep at p_final, then at p_approx
 //
-// Sphere records are built once per call (rm_prep_kernel) and read through the constant
+// Sphere records are built once per call (rm_prep_kernel; rm_records.h) and read through the constant
 // address space into SGPRs (vector sweeps, two spheres per packed instruction) or as bf16
 // MFMA fragments (march). The soft-min log-sum-exp runs in base 2 on v_exp_f32/v_log_f32 with
 // the cheapest provably safe shift. Per-sphere gradients are summed over the 64 rays of a
@@ -58,9 +58,8 @@ constexpr int kRedArrStride = 32;  // unsigneds between rm_reduce_partials' arri
 // kRender: the non-differentiable target renderer of renderer.rs:4-80 (generate.rs)
 enum Mode { kFwd = 0, kBwd = 1, kTrain = 2, kRender = 3 };
 
-// bounds the partial-gradient workspace per launch: 16 views of 512x512
-// 128 views of 512 x 512 in one launch (per-launch ramp-down and the per-call record, origin
-// and reduction launches amortised over all the views of a step)
+// bounds the partial-gradient workspace per launch: 128 views of 512 x 512 in one launch (per-launch
+// ramp-down and the per-call record, origin and reduction launches amortised over all the views of a step)
 constexpr int kMaxBlocksPerLaunch = 131072 * (256 / kBlock);
 // camera bases carried in the kernel arguments; calls with more views read a device table
 constexpr int kInlineCams = 16;
@@ -86,6 +85,7 @@ constexpr int kSplitRays = 32;  // (same box, the work-unit backward: C5 +3.5 %,
 static_assert(kSplitRays == 64 || kSplitRays == 32 || kSplitRays == 16, "split blocks hold 64, 32 or 16 rays");
 constexpr int kSplitCB = kSplitRays / 16;  // column blocks of 16 rays in the split march's tiles
 constexpr long long kSplitMaxRays = 262144;
+constexpr int kStatsWords = 6;  // rm_stats device counters (KArgs::stats)
 constexpr int kReduceSegs = 128;  // block segments of the reduction (128: 12.6 + 6.9 us at 10 views vs 20.3 + 4.9 with 64)
 
 struct KArgs {
@@ -106,7 +106,7 @@ struct KArgs {
   int early_exit;             // waves whose rays are all gone stop marching
   int proof;                  // the escape proof before the march (rm_ray_kernel<.., PROOF>; march_policy): 1 the
                               // soft ball alone, 2 with the call's lattice
-  int split;                  // split march (RM_MARCH_SPLIT): 64 rays per block, a quarter of the spheres per wave
+  int split;                  // split march (RM_MARCH_SPLIT): kSplitRays rays per block, a quarter of the spheres per wave
   int mfma;                   // march sums on the matrix cores (lse_mfma) instead of lse_weighted
   int shift_max;              // RM_MARCH_FORCE_MAX_SHIFT: every march step takes the running-max shift
   const int* esc_flags;       // nullable: per-block escape flags of this launch (rm_escape_kernel)
@@ -199,91 +199,6 @@ __device__ __forceinline__ void trace_word(const KArgs& a, int w, unsigned long 
 #define RM_TRACE(w, v) ((void)0)
 #endif
 
-// ---- sphere records: pair-interleaved, in global memory, read through scalar loads ----------
-// rm_prep_kernel writes them once per call. Pair i holds spheres (2i, 2i+1) so every sweep runs
-// two spheres per v_pk_* instruction:
-//   P0 = {-2cx0, -2cx1, -2cy0, -2cy1}   P1 = {-2cz0, -2cz1, |c0|^2, |c1|^2}
-//   P2 = {k r0, k r1, r0, r1}           P3 = {red0, red1, green0, green1}   P4 = {blue0, blue1}
-//   S0, S1 = P0, P1 scaled by k^2       W  = {2^(k r0), 2^(k r1), 2^(k (r0 - r_first)), 2^(k (r1 - r_first))}
-// (k = smooth_k log2 e). Every lane of a wave reads the same record at the same time, so the
-// kernel reads them through the constant address space: s_load into SGPRs that feed the
-// packed VALU ops as scalar operands -- no LDS staging, no LDS broadcast traffic, and no limit
-// on M (the records stream through the scalar cache / L2).
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef float f2v __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(4))) f4v* cf4_ptr;
-typedef const __attribute__((address_space(4))) f2v* cf2_ptr;
-typedef const __attribute__((address_space(4))) float* cf1_ptr;
-
-// Header after the records: {r_min, r_max, max |c_j - c_0|, R_soft, c_x, c_y, c_z, R} of the real
-// spheres ((c, R): bounding sphere, scene_bound; R_soft: soft_radius), followed by one partial header per
-// rm_prep_kernel block when that kernel ran on more than one block.
-constexpr int kRecHeader = 8;
-
-// Then, 16-byte aligned, the matrix-core tiles of the march (lse_mfma): per row block of 16
-// spheres 64 lanes x 16 B of A fragments, then per row block 32 floats {w(16), w_fixed(16)}.
-__host__ __device__ inline size_t tiles_offset(int npairs, int nprep) {
-  return ((size_t)npairs * (7 * 16 + 8) + (size_t)(nprep + 1) * kRecHeader * sizeof(float) + 15) & ~(size_t)15;
-}
-// Then the escape thresholds of the march: kEscTab floats (see write_bound).
-constexpr int kEscTab = 64;
-constexpr int kStatsWords = 6;  // rm_stats device counters (KArgs::stats)
-__host__ __device__ inline size_t esc_offset(int npairs, int nprep) {
-  const size_t nrb = (size_t)npairs / 8;
-  return tiles_offset(npairs, nprep) + nrb * 64 * 16 + nrb * 32 * sizeof(float);
-}
-// Then the per-view origin steps of camera mode (write_origins): RM_MAX_VIEWS_PER_CALL floats,
-// then per view a lower bound on the eye's distance to the nearest sphere centre (the march's
-// clamp-free proof, rho_lb in rm_ray_kernel): RM_MAX_VIEWS_PER_CALL floats.
-__host__ __device__ inline size_t origin_offset(int npairs, int nprep) {
-  return esc_offset(npairs, nprep) + kEscTab * sizeof(float);
-}
-// Then the geometry of the call's escape lattice (write_bound; bound_proof in rm_ray_kernel), kLatGeom
-// floats: {x, y, z of cell centre 0, h, half-side, 1 / h, slack, 0}. It depends on the scene's bounding
-// sphere, which only the record kernel knows, so it lives here and not in KArgs.
-constexpr int kLatGeom = 8;
-__host__ __device__ inline size_t lattice_offset(int npairs, int nprep) {
-  return origin_offset(npairs, nprep) + 2 * RM_MAX_VIEWS_PER_CALL * sizeof(float);
-}
-__host__ __device__ inline size_t rec_bytes(int npairs, int nprep) {
-  return lattice_offset(npairs, nprep) + kLatGeom * sizeof(float);
-}
-
-struct Lds {  // the sphere records (global, scalar-loaded) plus the kernel's LDS scratch
-  cf4_ptr P0, P1, P2, P3, S0, S1, W;
-  cf2_ptr P4;
-  const uint4* At;  // lse_mfma sphere fragments (global)
-  const float* Wt;  // lse_mfma weights (global)
-  float* slots;  // LDS: the backward's ray images and shares; lse_mfma's ray exchange in the march
-  float* misc;   // small LDS scratch
-  __device__ __forceinline__ static float4 v4(f4v v) { return make_float4(v.x, v.y, v.z, v.w); }
-  __device__ __forceinline__ float4 p0(int i) const { return v4(P0[i]); }
-  __device__ __forceinline__ float4 p1(int i) const { return v4(P1[i]); }
-  __device__ __forceinline__ float4 p2(int i) const { return v4(P2[i]); }
-  __device__ __forceinline__ float4 p3(int i) const { return v4(P3[i]); }
-  __device__ __forceinline__ float2 p4(int i) const {
-    const f2v v = P4[i];
-    return make_float2(v.x, v.y);
-  }
-  __device__ __forceinline__ float2 kr(int i) const {
-    const f4v v = P2[i];
-    return make_float2(v.x, v.y);
-  }
-  // the same records from pair `off` on (a split block's quarter of the vector sweeps)
-  __device__ __forceinline__ Lds from_pair(int off) const {
-    Lds q = *this;
-    q.P0 += off;
-    q.P1 += off;
-    q.P2 += off;
-    q.P3 += off;
-    q.S0 += off;
-    q.S1 += off;
-    q.W += off;
-    q.P4 += off;
-    return q;
-  }
-};
-
 // LDS: the backward's ray images and g_t shares, or (during the march) lse_mfma's per-wave ray
 // exchange (64 x (16 + 16 + 4) B per wave); then 256 B of misc scratch.
 // The backward (one sphere per lane) uses 15 x 64 ray-data floats (field-major) per wave
@@ -298,84 +213,6 @@ __host__ __device__ constexpr size_t lds_bytes() { return kSlotBytes + 256; }
 // the split march's two combine buffers (kWaves x 64 floats each) after the march exchange
 constexpr int kSplitCombOff = kWaves * 64 * 9;  // floats: xa, xb (64 uint4 per wave each), xs
 static_assert((kSplitCombOff + 2 * kWaves * 64) * sizeof(float) <= kSlotBytes, "split combine buffers fit the slots");
-
-// three-value block reduction (min, max, max) for the record header (blockDim.x / 64 <= 16 waves)
-__device__ __forceinline__ void header_reduce(float& rmin, float& rmax, float& spread, float* dst) {
-  __shared__ float red[3][16];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    rmin = fminf(rmin, __shfl_xor(rmin, off));
-    rmax = fmaxf(rmax, __shfl_xor(rmax, off));
-    spread = fmaxf(spread, __shfl_xor(spread, off));
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[0][wave] = rmin;
-    red[1][wave] = rmax;
-    red[2][wave] = spread;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w2 = 1; w2 < (int)(blockDim.x >> 6); ++w2) {
-      red[0][0] = fminf(red[0][0], red[0][w2]);
-      red[1][0] = fmaxf(red[1][0], red[1][w2]);
-      red[2][0] = fmaxf(red[2][0], red[2][w2]);
-    }
-    dst[0] = red[0][0];
-    dst[1] = red[1][0];
-    dst[2] = red[2][0];
-    dst[3] = 0.0f;
-  }
-}
-
-// Bounding sphere of the scene, block-wide: c0 = centre of the centres' bounding box,
-// R >= |c_j - c0| + r_j for every sphere (rounded up). scratch: >= 8 floats of LDS per wave of
-// the block.
-__device__ __forceinline__ void scene_bound(const KArgs& a, float* scratch, int tid, float c0[3], float& R) {
-  const int lane = tid & 63, wave = tid >> 6, nt = (int)blockDim.x, nw = nt >> 6;
-  float v[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  for (int j = tid; j < a.M; j += nt)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const float c = a.centers[3 * j + k];
-      v[k] = fminf(v[k], c);
-      v[3 + k] = fmaxf(v[3 + k], c);
-    }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      v[k] = fminf(v[k], __shfl_xor(v[k], off));
-      v[3 + k] = fmaxf(v[3 + k], __shfl_xor(v[3 + k], off));
-    }
-  if (lane == 0)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) scratch[8 * wave + k] = v[k];
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    float lo = scratch[k], hi = scratch[3 + k];
-    for (int w = 1; w < nw; ++w) {
-      lo = fminf(lo, scratch[8 * w + k]);
-      hi = fmaxf(hi, scratch[8 * w + 3 + k]);
-    }
-    c0[k] = 0.5f * (lo + hi);
-  }
-  float r = 0.0f;
-  for (int j = tid; j < a.M; j += nt) {
-    const float dx = a.centers[3 * j] - c0[0], dy = a.centers[3 * j + 1] - c0[1], dz = a.centers[3 * j + 2] - c0[2];
-    r = fmaxf(r, fsqrt(dx * dx + dy * dy + dz * dz) + a.radius[j]);  // 1 ulp: inside the round-up below
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) r = fmaxf(r, __shfl_xor(r, off));
-  __syncthreads();  // everyone has read the box
-  if (lane == 0) scratch[8 * wave] = r;
-  __syncthreads();
-  R = scratch[0];
-  for (int w = 1; w < nw; ++w) R = fmaxf(R, scratch[8 * w]);
-  R = R * (1.0f + 1e-5f) + 1e-6f;  // cover the f32 rounding of |c - c0| + r
-  __syncthreads();  // scratch is reused by the caller
-}
 
 // ---- matrix-core march fragments (see lse_mfma) ----------------------------------------------
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
@@ -428,243 +265,7 @@ __device__ __forceinline__ uint4 mfma_a_frag(const KArgs& a, int e) {
 __device__ __forceinline__ int mfma_w_sphere(int e) { return 16 * (e >> 5) + (e & 15); }
 __device__ __forceinline__ bool mfma_w_fixed(int e) { return (e & 16) != 0; }
 
-// The soft radius of the scene about c0 (hdr[3]; the escape proof's bound, bound_proof in
-// rm_ray_kernel): R_soft = (1/k) ln sum_j exp(k (|c_j - c0| + r_j)), rounded up. Every sphere has
-// |p - c_j| >= |p - c0| - |c_j - c0|, so exp(-k (|p - c_j| - r_j)) <= exp(-k |p - c0|)
-// exp(k (|c_j - c0| + r_j)); summed over j, the soft-min D(p) >= |p - c0| - R_soft at every p (the
-// padding spheres add 0 to D's sum in fp32, the clamp max(q, 1e-6) only raises D). R <= R_soft <=
-// R + ln(M)/k: the ball bound |p - c0| - R - ln(M)/k charges every sphere as if it sat at the rim.
-// In fp32, relative to R of scene_bound: v_j = (|c_j - c0| + r_j) (1 + 1e-5) + 1e-6 is scene_bound's
-// own rounded-up term, so v_j <= R and every exponent is <= 0; the sum (a term's relative error
-// below 2e-6 where it matters, at most M / 256 + 14 additions per chain) is taken 1e-5 up, the
-// logarithm's 1e-7 and the division go into the final 1e-5 relative + 1e-6. scratch as scene_bound's.
-// The escape proof runs from kProofMinSpheres (padded) spheres on: a bound step costs about a tenth
-// of a real march step at 64 spheres, and the C2 shape (256x256, 64 spheres, 10 views) ran 1.6 %
-// slower with the proof. A call without the proof (KArgs::proof, march_policy) launches the kernel
-// instance without it, and its record kernel skips the pass: hdr[3] = R + ln(M)/k, the ball's bound.
-constexpr int kProofMinSpheres = 128;
-// The escape lattice of the camera-mode proof (bound_proof; KArgs::lattice): kLatticeN^3 cells over the cube
-// of half-side R' + kLatticeMargin about c_0. Sized by tools/escape_proof_sim.py on the bench scene after
-// 35 optimizer steps (profiles/r19_escape_lattice_sim.txt): 64 cells save 26.7 % of the march's packed
-// column blocks where the soft ball alone saves 2.9 %; 96 / 128 add 2 / 4 points for 3.4 / 8 times the fill
-// and a table of 3.5 / 8 MB against the 4 MB L2; the margin hardly matters (0.1 / 0.25 / 0.5: 27.0 / 26.7 / 25.7 %).
-constexpr int kLatticeN = 64;
-constexpr float kLatticeMargin = 0.25f;
-__device__ __forceinline__ float soft_radius(const KArgs& a, float* scratch, int tid, const float c0[3], float R) {
-  const int lane = tid & 63, wave = tid >> 6, nt = (int)blockDim.x, nw = nt >> 6;
-  const float kappa = a.k * kLog2e;
-  float s = 0.0f;
-  for (int j = tid; j < a.M; j += nt) {
-    const float dx = a.centers[3 * j] - c0[0], dy = a.centers[3 * j + 1] - c0[1], dz = a.centers[3 * j + 2] - c0[2];
-    const float v = (fsqrt(dx * dx + dy * dy + dz * dz) + a.radius[j]) * (1.0f + 1e-5f) + 1e-6f;
-    s += fexp2(kappa * fminf(v - R, 0.0f));
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  if (lane == 0) scratch[8 * wave] = s;
-  __syncthreads();
-  float sum = scratch[0];
-  for (int w = 1; w < nw; ++w) sum += scratch[8 * w];
-  __syncthreads();  // scratch is reused by the caller
-  // sum >= 1 up to rounding (the sphere that sets R has exponent ~0); never above the ball's slack
-  const float rs = (R + flog2(fmaxf(sum, 1.0f) * (1.0f + 1e-5f)) / kappa) * (1.0f + 1e-5f) + 1e-6f;
-  return fminf(rs, R + a.lse_slack);
-}
-
-// hdr[4..7] = the bounding sphere (c, R) of scene_bound, for the march's escape test, and its
-// distance thresholds T(n), n < kEscTab: a receding ray at distance d from c with n march steps
-// left ends them at distance >= gone_d + R' from c if (1 - 1e-5) d >= T(n). Every step is at
-// least g = d - R' long (R' = R + ln(M)/k + 1e-3: the soft-min is >= the hard min - ln(M)/k,
-// 1e-3 covers the fp32 march) and keeps the ray receding, so one step takes d to at least
-// F(d) = (1 - 1e-5) sqrt(d^2 + (d - R')^2); T(0) = gone_d + R' and T(n) = F^-1(T(n - 1)) =
-// (R' + sqrt(2 y^2 - R'^2)) / 2 with y = T(n - 1) / (1 - 1e-5), rounded up. For n >= kEscTab the
-// march uses T(kEscTab - 1) >= T(n).
-__device__ void write_bound(const KArgs& a, float* hdr, float* esc) {
-  __shared__ float scratch[8 * 16];
-  float c[3], R;
-  scene_bound(a, scratch, threadIdx.x, c, R);
-  const float rsoft = a.proof ? soft_radius(a, scratch, threadIdx.x, c, R)
-                                                                    : R + a.lse_slack;
-  if (threadIdx.x == 0) {
-    hdr[3] = rsoft;
-    hdr[4] = c[0];
-    hdr[5] = c[1];
-    hdr[6] = c[2];
-    hdr[7] = R;
-    if (a.lattice != nullptr) {
-      // The escape lattice of this call (kLatticeN; rm_lattice_kernel fills it, bound_proof reads it): the
-      // cube of half-side R' + kLatticeMargin about c_0 in kLatticeN^3 cells of side h, cell i's centre at
-      // -half + (i + 0.5) h per axis. The division is done here, once: the ray kernel multiplies by 1 / h.
-      // slack: see bound_proof.
-      float* lat = esc + kEscTab + 2 * RM_MAX_VIEWS_PER_CALL;
-      const float half = (R + a.lse_slack + 1e-3f) * (1.0f + 1e-6f) + kLatticeMargin;
-      const float h = 2.0f * half / (float)kLatticeN;
-      for (int k = 0; k < 3; ++k) lat[k] = (c[k] - half) + 0.5f * h;
-      lat[3] = h;
-      lat[4] = half;
-      lat[5] = 1.0f / h;
-      lat[6] = h * (0.8660254f * (1.0f + 1e-4f)) + 1e-3f;
-      lat[7] = 0.0f;
-    }
-  }
-  if (threadIdx.x < kEscTab) {
-    // f32 with a 1e-5 relative + 1e-6 absolute round-up per iteration (the f32 rounding of one
-    // iteration is a few 1e-7): every T(n) stays above the exact inverse iterate. (R' rounded up
-    // is conservative too: F^-1 grows with R' for y > R', which holds along the table.)
-    float tv = INFINITY;
-    if (a.gone_d > 0.0f) {
-      const float rp = (R + a.lse_slack + 1e-3f) * (1.0f + 1e-6f);
-      const float inv_shrink = 1.0000101f;  // y = T / (1 - 1e-5) <= T inv_shrink
-      float T = (a.gone_d + rp) * (1.0f + 1e-6f);
-      // four dependent instructions per step (v_sqrt_f32: 1 ulp, inside the round-up)
-      const float two_c2 = 2.0f * inv_shrink * inv_shrink * (1.0f + 1e-6f), nrp2 = -rp * rp,
-                  half_up = 0.5f * (1.0f + 1e-5f);
-      // the march reads T(n) for n <= a.steps only: entries past it repeat T(a.steps) (>= T(n)),
-      // which shortens the longest dependent chain at S < kEscTab
-      const int nmax = min((int)threadIdx.x, a.steps);
-      for (int n = 1; n <= nmax; ++n) T = fmaf(rp + fsqrt(fmaf(two_c2 * T, T, nrp2)), half_up, 1e-6f);
-      tv = T * (1.0f + 1e-6f);
-    }
-    esc[threadIdx.x] = tv;
-  }
-}
-
-// Records of the call (see Lds), one thread per sphere pair. Each block reduces its pairs'
-// {r_min, r_max, spread} into the header (one block) or its partial (several blocks, then
-// rm_prep_finish); the final header also gets the scene's bounding sphere (scene_bound).
-constexpr int kPrepStageMax = 512;  // one-block prep: parameters staged in LDS up to this M
-
-template <bool PAR>
-__device__ void write_origins(const KArgs& a, const float4& S00, const float4& S10, float rmax, float spread,
-                              const uint4* At, const float* Wt, float* orig, unsigned char* xch, int v);
-
-__global__ __launch_bounds__(256) void rm_prep_kernel(const KArgs a0, float4* __restrict__ rec) {
-  // One-block case: stage the parameters in LDS once (one load round instead of one per phase:
-  // records, MFMA tiles, header, bounding sphere); the phases below read them through `a`.
-  __shared__ float stage[7 * kPrepStageMax];
-  const int nt = (int)blockDim.x;
-  KArgs a = a0;
-  if (gridDim.x == 1 && a0.M <= kPrepStageMax) {
-    const int M = a0.M;
-    for (int e = threadIdx.x; e < 3 * M; e += nt) {
-      stage[e] = a0.centers[e];
-      stage[3 * M + e] = a0.colors_h != nullptr ? (float)a0.colors_h[e] : a0.colors[e];
-    }
-    for (int e = threadIdx.x; e < M; e += nt) stage[6 * M + e] = a0.radius[e];
-    __syncthreads();
-    a.centers = stage;
-    a.colors = stage + 3 * M;
-    a.colors_h = nullptr;
-    a.radius = stage + 6 * M;
-  }
-  const int np = a.Mpad / 2;
-  float4* P0 = rec;
-  float4* P1 = P0 + np;
-  float4* P2 = P1 + np;
-  float4* P3 = P2 + np;
-  float4* S0 = P3 + np;
-  float4* S1 = S0 + np;
-  float4* W = S1 + np;
-  float2* P4 = reinterpret_cast<float2*>(W + np);
-  float* hdr = reinterpret_cast<float*>(P4 + np);
-  const float kappa = a.k * kLog2e, k2 = kappa * kappa;
-  const float kr_first = kappa * a.radius[0];
-  const float c0x = a.centers[0], c0y = a.centers[1], c0z = a.centers[2];
-  float rmin = INFINITY, rmax = 0.0f, spread = 0.0f;
-  const int ip = blockIdx.x * nt + threadIdx.x;
-  if (ip < np) {
-    float gx[2], gy[2], gz[2], cc[2], kr[2], rr[2], cr[2], cg[2], cb[2], w[2], wf[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int j = 2 * ip + h;
-      if (j < a.M) {
-        const float cx = a.centers[3 * j], cy = a.centers[3 * j + 1], cz = a.centers[3 * j + 2];
-        const float r = a.radius[j];
-        gx[h] = -2.0f * cx;
-        gy[h] = -2.0f * cy;
-        gz[h] = -2.0f * cz;
-        cc[h] = cx * cx + cy * cy + cz * cz;
-        kr[h] = kappa * r;
-        rr[h] = r;
-        if (a.colors_h != nullptr) {  // fp16 colours: widened exactly, blended in fp32
-          cr[h] = (float)a.colors_h[3 * j];
-          cg[h] = (float)a.colors_h[3 * j + 1];
-          cb[h] = (float)a.colors_h[3 * j + 2];
-        } else {
-          cr[h] = a.colors[3 * j];
-          cg[h] = a.colors[3 * j + 1];
-          cb[h] = a.colors[3 * j + 2];
-        }
-        w[h] = fexp2(kr[h]);
-        wf[h] = fexp2(kr[h] - kr_first);
-        rmin = fminf(rmin, r);
-        rmax = fmaxf(rmax, r);
-        const float ex = cx - c0x, ey = cy - c0y, ez = cz - c0z;
-        spread = fmaxf(spread, sqrtf(ex * ex + ey * ey + ez * ez));
-      } else {
-        // padding sphere at c = (kPadCenter, 0, 0): the expansion form (|c|^2) and the direct
-        // form of the normal taps (p - c) both see distance ~1e15, so every exp() of its terms
-        // underflows to exactly 0 (its weights are 0) and all of its gradient terms are 0.
-        gx[h] = -2.0f * kPadCenter;
-        gy[h] = gz[h] = 0.0f;
-        cc[h] = kPadCenter * kPadCenter;
-        kr[h] = rr[h] = cr[h] = cg[h] = cb[h] = w[h] = wf[h] = 0.0f;
-      }
-    }
-    P0[ip] = make_float4(gx[0], gx[1], gy[0], gy[1]);
-    P1[ip] = make_float4(gz[0], gz[1], cc[0], cc[1]);
-    P2[ip] = make_float4(kr[0], kr[1], rr[0], rr[1]);
-    P3[ip] = make_float4(cr[0], cr[1], cg[0], cg[1]);
-    P4[ip] = make_float2(cb[0], cb[1]);
-    S0[ip] = make_float4(k2 * gx[0], k2 * gx[1], k2 * gy[0], k2 * gy[1]);
-    S1[ip] = make_float4(k2 * gz[0], k2 * gz[1], k2 * cc[0], k2 * cc[1]);
-    W[ip] = make_float4(w[0], w[1], wf[0], wf[1]);
-  }
-  // matrix-core tiles of the march (lse_mfma)
-  const int nrb = np / 8;
-  char* tiles = reinterpret_cast<char*>(rec) + tiles_offset(np, gridDim.x);
-  uint4* At = reinterpret_cast<uint4*>(tiles);
-  float* Wt = reinterpret_cast<float*>(At + (size_t)nrb * 64);
-  for (int e = blockIdx.x * nt + threadIdx.x; e < nrb * 64; e += gridDim.x * nt) At[e] = mfma_a_frag(a, e);
-  for (int e = blockIdx.x * nt + threadIdx.x; e < nrb * 32; e += gridDim.x * nt) {
-    const int j = mfma_w_sphere(e);
-    const float krj = j < a.M ? kappa * a.radius[j] : 0.0f;
-    Wt[e] = j >= a.M ? 0.0f : (mfma_w_fixed(e) ? fexp2(krj - kr_first) : fexp2(krj));
-  }
-  header_reduce(rmin, rmax, spread, gridDim.x == 1 ? hdr : hdr + (size_t)(1 + blockIdx.x) * kRecHeader);
-  if (gridDim.x == 1) write_bound(a, hdr, reinterpret_cast<float*>(reinterpret_cast<char*>(rec) + esc_offset(np, 1)));
-}
-
-__global__ __launch_bounds__(256) void rm_prep_finish(const KArgs a, float* __restrict__ hdr, float* __restrict__ esc,
-                                                      int nprep) {
-  float rmin = INFINITY, rmax = 0.0f, spread = 0.0f;
-  for (int b = threadIdx.x; b < nprep; b += 256) {
-    const float* h = hdr + (size_t)(1 + b) * kRecHeader;
-    rmin = fminf(rmin, h[0]);
-    rmax = fmaxf(rmax, h[1]);
-    spread = fmaxf(spread, h[2]);
-  }
-  header_reduce(rmin, rmax, spread, hdr);
-  write_bound(a, hdr, esc);
-}
-
-// The per-view origin steps (write_origins), one 64-thread block (one wave) per view, after the
-// records are complete: the views run on separate CUs side by side.
-// A split launch's origin step runs its four quarters on four waves of the block (the split
-// march's own combine: the same bits).
-constexpr int kOriginXch = 64 * 36;  // bytes of march exchange per wave
-template <bool SPLIT>
-__global__ __launch_bounds__(SPLIT ? 64 * kSplitWaves : 64) void rm_origin_kernel(const KArgs a,
-                                                                                 const float4* __restrict__ rec,
-                                                                                 int nprep) {
-  __shared__ __attribute__((aligned(16))) unsigned char xch[SPLIT ? kSplitWaves * kOriginXch + kSplitWaves * 64 * 4
-                                                                  : kOriginXch];
-  const int np = a.Mpad / 2;
-  const uint4* At = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(rec) + tiles_offset(np, nprep));
-  const float* Wt = reinterpret_cast<const float*>(At + (size_t)(np / 8) * 64);
-  const float* hdr = reinterpret_cast<const float*>(reinterpret_cast<const float2*>(rec + 7 * (size_t)np) + np);
-  write_origins<SPLIT>(a, rec[4 * np], rec[5 * np], hdr[1], hdr[2], At, Wt, a.origin, xch, blockIdx.x);
-}
+#include "rm_records.h"
 
 // ---- packed helpers --------------------------------------------------------------------------
 __device__ __forceinline__ f2 sp(float x) { return f2{x, x}; }
@@ -1049,7 +650,7 @@ __device__ void write_origins(const KArgs& a, const float4& S00, const float4& S
       D = march_d_none<true>(p, kappa, inv_kappa, Aq, Wq, nq, xa, xb, xs, lane, comb, wave);
     else if (a.mfma && shift_fixed_ok && psq(p) <= 1e10f)
       D = march_d_fixed<true>(p, kappa, inv_kappa, kr_first, S00, S10, Aq, Wq, nq, xa, xb, xs, lane, comb, wave);
-    if (lane == 0 && wave == 0) orig[v] = D;
+    if (lane == 0 && wave == 0) orig[RecTail::kD0 + v] = D;
     // the eye's distance to the nearest sphere centre (direct form), rounded down by a relative
     // 1e-6 and 1e-6 (1 + |eye|) against the fp32 rounding of the eye and of the centres' offsets
     float m2 = INFINITY;
@@ -1067,7 +668,7 @@ __device__ void write_origins(const KArgs& a, const float4& S00, const float4& S
       for (int w = 0; w < kSplitWaves; ++w) m2 = fminf(m2, wmin[w]);
     }
     if (lane == 0 && wave == 0)
-      orig[RM_MAX_VIEWS_PER_CALL + v] =
+      orig[RecTail::kRhoLb + v] =
           sqrtf(m2) * (1.0f - 1e-6f) - 1e-6f * (1.0f + fabsf(p[0]) + fabsf(p[1]) + fabsf(p[2]));
   }
 }

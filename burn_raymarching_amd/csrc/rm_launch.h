@@ -372,17 +372,17 @@ int fill_camera_args(rm_context* ctx, const Geometry& g, KArgs& a) {
 // eye, shared by every ray of the view (rm_origin_kernel); a.origin is set before the record
 // kernels, which take the whole KArgs.
 int prepare_records(rm_context* ctx, KArgs& a, bool origin) {
-  const int np = a.Mpad / 2, nprep = (np + 255) / 256;
+  const RecLayout lay(a.Mpad);
+  const int nprep = lay.nprep();
   int rc;
-  if ((rc = ctx->rec.ensure(ctx, rec_bytes(np, nprep), "record buffer")) != RM_OK) return rc;
+  if ((rc = ctx->rec.ensure(ctx, lay.bytes(), "record buffer")) != RM_OK) return rc;
   char* rec = ctx->rec.as<char>();
-  a.origin = origin ? reinterpret_cast<float*>(rec + origin_offset(np, nprep)) : nullptr;
+  a.origin = origin ? RecLayout::at<float>(rec, lay.origin(RecTail::kD0)) : nullptr;
   hipLaunchKernelGGL(rm_prep_kernel, dim3(nprep), dim3(256), 0, ctx->stream, a, (float4*)rec);
   RM_HIP(ctx, hipGetLastError());
   if (nprep > 1) {
-    float* hdr = reinterpret_cast<float*>(rec + (size_t)np * (7 * 16 + 8));
-    float* esc = reinterpret_cast<float*>(rec + esc_offset(np, nprep));
-    hipLaunchKernelGGL(rm_prep_finish, dim3(1), dim3(256), 0, ctx->stream, a, hdr, esc, nprep);
+    hipLaunchKernelGGL(rm_prep_finish, dim3(1), dim3(256), 0, ctx->stream, a, RecLayout::at<float>(rec, lay.header()),
+                       RecLayout::at<float>(rec, lay.esc()), nprep);
     RM_HIP(ctx, hipGetLastError());
   }
   if (origin) {
@@ -404,7 +404,6 @@ int prepare_records(rm_context* ctx, KArgs& a, bool origin) {
 // stream: the scene changes with every optimizer step, so nothing of it is kept across calls.
 constexpr size_t kLatticeCells = (size_t)kLatticeN * kLatticeN * kLatticeN;
 int fill_lattice(rm_context* ctx, const KArgs& a) {
-  const int np = a.Mpad / 2;
   SdfArgs s;
   std::memset(&s, 0, sizeof s);
   s.rec_buf = a.rec_buf;
@@ -414,7 +413,7 @@ int fill_lattice(rm_context* ctx, const KArgs& a) {
   s.nx = kLatticeN;
   s.ny = kLatticeN;
   s.dist = const_cast<float*>(a.lattice);
-  s.geom = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.rec_buf) + lattice_offset(np, (np + 255) / 256));
+  s.geom = RecLayout::at<const float>(a.rec_buf, RecLayout(a.Mpad).lattice());
   static_assert(kLatticeCells % kBlock == 0 && kLatticeCells / kBlock <= kMaxBlocksPerLaunch, "one launch");
   hipLaunchKernelGGL(rm_lattice_kernel, dim3((unsigned)(kLatticeCells / kBlock)), dim3(kBlock), 0, ctx->stream, s);
   RM_HIP(ctx, hipGetLastError());
@@ -1060,6 +1059,21 @@ int run_raygrad(rm_context* ctx, const RayGradCall& c) {
   return RM_OK;
 }
 
+// The records of a scene-only call (run_view, run_sdf). The record kernel takes the scene and k through a march
+// description, m (of its flags only the colour format counts): checks both, then if `launch` fills a and runs it.
+int scene_records(rm_context* ctx, const rm_scene* scene, bool need_light, rm_march m, bool launch, KArgs& a) {
+  int rc;
+  m.mask_sharpness = 0.0f;
+  m.flags &= RM_MARCH_COLOR_F16;
+  const Geometry g = ray_geometry(nullptr, nullptr, 0, scene, &m);
+  if ((rc = check_scene(ctx, scene, need_light)) != RM_OK) return rc;
+  if ((rc = check_march(ctx, &m)) != RM_OK) return rc;
+  std::memset(&a, 0, sizeof a);
+  if (!launch) return RM_OK;
+  fill_scene_args(g, a);
+  return prepare_records(ctx, a, false);
+}
+
 // ---- the viewer's frame render (rm_view.h) ---------------------------------------------------
 
 // viewer.rs:65-86 / shader.wgsl:108-110 in f32: ro and the basis ww, uu = ww x up, vv = uu x ww
@@ -1086,24 +1100,15 @@ int run_view(rm_context* ctx, const rm_view_camera* cams, int frames, int W, int
              const rm_view_params& vp, float* out_rgb, uint8_t* out_rgba8, float* out_depth) {
   ctx->opt_prepared = false;
   int rc;
-  // the record kernel takes the scene and k through a march description
   rm_march m;
   rm_march_default(&m);
   m.steps = vp.max_steps;
   m.smooth_k = vp.smooth_k;
   m.normal_eps = vp.normal_eps;
   m.color_sharpness = vp.color_sharpness;
-  m.mask_sharpness = 0.0f;
-  m.flags = vp.flags & RM_MARCH_COLOR_F16;
-  Geometry g;
-  g.scene = scene;
-  g.march = &m;
-  if ((rc = check_scene(ctx, scene, true)) != RM_OK) return rc;
-  if ((rc = check_march(ctx, &m)) != RM_OK) return rc;
+  m.flags = vp.flags;
   KArgs a;
-  std::memset(&a, 0, sizeof a);
-  fill_scene_args(g, a);
-  if ((rc = prepare_records(ctx, a, false)) != RM_OK) return rc;
+  if ((rc = scene_records(ctx, scene, true, m, true, a)) != RM_OK) return rc;
 
   ViewArgs v;
   std::memset(&v, 0, sizeof v);
@@ -1150,23 +1155,14 @@ int run_sdf(rm_context* ctx, bool grid, const float* points, long long n, const 
             int ny, const rm_scene* scene, const rm_sdf_params& sp, float* dist, float* grad, float* color) {
   ctx->opt_prepared = false;
   int rc;
-  // the record kernel takes the scene and k through a march description
   rm_march m;
   rm_march_default(&m);
   m.smooth_k = sp.smooth_k;
   m.color_sharpness = sp.color_sharpness;
-  m.mask_sharpness = 0.0f;
-  m.flags = sp.flags & RM_MARCH_COLOR_F16;
-  Geometry g;
-  g.scene = scene;
-  g.march = &m;
-  if ((rc = check_scene(ctx, scene, false)) != RM_OK) return rc;
-  if ((rc = check_march(ctx, &m)) != RM_OK) return rc;
-  if (n == 0) return RM_OK;
+  m.flags = sp.flags;
   KArgs a;
-  std::memset(&a, 0, sizeof a);
-  fill_scene_args(g, a);
-  if ((rc = prepare_records(ctx, a, false)) != RM_OK) return rc;
+  if ((rc = scene_records(ctx, scene, false, m, n != 0, a)) != RM_OK) return rc;
+  if (n == 0) return RM_OK;
 
   SdfArgs s;
   std::memset(&s, 0, sizeof s);

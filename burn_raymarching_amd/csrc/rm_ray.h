@@ -1,6 +1,6 @@
-// rm_ray.h -- the fused per-ray kernel (rm_ray_kernel), included by rm_kernels.hip after the
-// sweeps and helpers it is built from: the continuation state's layout (ContState), the record
-// binding and the backward's small helpers, then ray_entry / rm_ray_kernel and ray_body.
+// rm_ray.h -- the fused per-ray kernel (rm_ray_kernel), included by rm_kernels.hip after rm_records.h
+// and the sweeps and helpers it is built from: the continuation state's layout (ContState), the record
+// binding plus LDS scratch (bind_lds) and the backward's small helpers, then ray_entry / rm_ray_kernel and ray_body.
 // ray_body runs the phases of DESIGN.md §4.2 in order -- block setup, march, continuation save /
 // restore, post-march forward, seeds, hand-off, backward -- as one function whose phases are lambdas
 // over its locals: the kernels sit at their register budget (117-123 of 128 VGPRs, SGPRs spilled
@@ -64,20 +64,9 @@ struct ContState {
   }
 };
 
-// The record pointers of the call (rm_prep_kernel's layout) and the kernel's LDS scratch.
+// The record pointers of the call (bind_records) and the kernel's LDS scratch.
 __device__ __forceinline__ Lds bind_lds(const KArgs& a, unsigned char* smem) {
-  Lds L;
-  const int np = a.Mpad / 2;
-  L.P0 = (cf4_ptr)a.rec_buf;
-  L.P1 = L.P0 + np;
-  L.P2 = L.P1 + np;
-  L.P3 = L.P2 + np;
-  L.S0 = L.P3 + np;
-  L.S1 = L.S0 + np;
-  L.W = L.S1 + np;
-  L.P4 = (cf2_ptr)(L.W + np);
-  L.At = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.rec_buf) + tiles_offset(np, (np + 255) / 256));
-  L.Wt = reinterpret_cast<const float*>(L.At + (size_t)(np / 8) * 64);
+  Lds L = bind_records(a.rec_buf, a.Mpad);
   L.slots = reinterpret_cast<float*>(smem);
   L.misc = L.slots + kSlotBytes / sizeof(float);
   return L;
@@ -85,25 +74,25 @@ __device__ __forceinline__ Lds bind_lds(const KArgs& a, unsigned char* smem) {
 
 // ---- backward helpers --------------------------------------------------------------------------
 // The sphere of a lane in the backward sweeps: sphere j of pair j / 2 from the records of
-// rm_prep_kernel (R4 by pair, R2 the blue pairs; np pairs), past Mpad the padding sphere.
+// rm_prep_kernel (R4 the buffer, R2 its blue pairs), past Mpad the padding sphere.
 // COLOUR (sweep 1): r and the colour; else (sweep 2) k r.
 struct LaneSphere {
   float gx = -2.0f * kPadCenter, gy = 0.0f, gz = 0.0f, cc = kPadCenter * kPadCenter;  // -2 c, |c|^2
   float kr = 0.0f, rr = 0.0f, cr = 0.0f, cg = 0.0f, cbl = 0.0f;
 };
 template <bool COLOUR>
-__device__ __forceinline__ LaneSphere load_sphere(const float4* R4, const float2* R2, int np, int j, int Mpad) {
+__device__ __forceinline__ LaneSphere load_sphere(const float4* R4, const float2* R2, const RecLayout& lay, int j, int Mpad) {
   LaneSphere s;
   if (j < Mpad) {
     const int i = j >> 1;
     const bool h = (j & 1) != 0;
-    const float4 A = R4[i], B = R4[np + i], R = R4[2 * np + i];
+    const float4 A = R4[lay.pair(RecLayout::kP0, i)], B = R4[lay.pair(RecLayout::kP1, i)], R = R4[lay.pair(RecLayout::kP2, i)];
     s.gx = h ? A.y : A.x;
     s.gy = h ? A.w : A.z;
     s.gz = h ? B.y : B.x;
     s.cc = h ? B.w : B.z;
     if constexpr (COLOUR) {
-      const float4 C3 = R4[3 * np + i];
+      const float4 C3 = R4[lay.pair(RecLayout::kP3, i)];
       const float2 C4 = R2[i];
       s.rr = h ? R.w : R.z;
       s.cr = h ? C3.y : C3.x;
@@ -225,8 +214,8 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   // Scene radius bounds from the record header: with r_min, a lower bound on the scene distance
   // proves rho_j = dist_j + r_j >= kSafeRho for every sphere, so max(q, 1e-6) cannot bind and
   // the sweeps may skip it (exactly the same results).
-  const cf1_ptr hdr = (cf1_ptr)(L.P4 + a.Mpad / 2);
-  const float rmin = hdr[0], rmax = hdr[1], spread = hdr[2];
+  const cf1_ptr hdr = rec_header(L, a.Mpad);
+  const float rmin = hdr[Hdr::kRmin], rmax = hdr[Hdr::kRmax], spread = hdr[Hdr::kSpread];
   // Block-uniform permissions for the cheaper log-sum-exp shifts of the march:
   // |v_j - v_0| = kappa |r_j - r_0 - (rho_j - rho_0)| <= kappa (r_max + |c_j - c_0|); v <= kappa r_max;
   // the weighted form 2^(k r) 2^(-k rho) also needs 2^(-k rho) of the nearest sphere normal:
@@ -482,8 +471,8 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   int steps_saved = 0;     // wave-uniform: march steps this wave did not run (work statistics)
   // the scene's bounding sphere (c, R) (scene_bound, in the record header); R' = R + soft-min
   // slack + 1e-3 (fp32 margin of the march)
-  const float c0x = hdr[4], c0y = hdr[5], c0z = hdr[6];
-  const cf1_ptr esc_tab = (cf1_ptr)(reinterpret_cast<const char*>(a.rec_buf) + esc_offset(a.Mpad / 2, (a.Mpad / 2 + 255) / 256));
+  const float c0x = hdr[Hdr::kCx], c0y = hdr[Hdr::kCy], c0z = hdr[Hdr::kCz];
+  const cf1_ptr esc_tab = (cf1_ptr)RecLayout::at<const char>(a.rec_buf, RecLayout(a.Mpad).esc());
   if (MODE == kBwd && a.t_in != nullptr) {
     t = a.t_in[ri];
   } else {
@@ -502,7 +491,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // the whole wave: 48 % of the march steps at 4096 spheres / 128 steps). A wave whose
     // rays are all gone stops (a.early_exit). The same in every mode that builds the table,
     // exit on or off, so both give the same bits.
-    const float rprime = (hdr[7] + a.lse_slack + 1e-3f) * (1.0f + 1e-6f);  // R' as in write_bound
+    const float rprime = (hdr[Hdr::kR] + a.lse_slack + 1e-3f) * (1.0f + 1e-6f);  // R' as in write_bound
     float gone_step = 0.0f;  // dist - R' of a gone ray at the current point
     auto wave_escaped = [&](int st, const float p[3]) {
       if (!(a.gone_d > 0.0f)) return false;
@@ -570,17 +559,16 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       // a wave vote: origins differ per lane (array mode; a wave across two views), and every lane
       // takes part in the votes below and must leave with the same answer (dead is wave-uniform)
       if (__any(!(onorm + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= 256.0f))) return false;
-      const float rs = (hdr[3] + 1e-3f) * (1.0f + 1e-6f) + 1e-3f;
+      const float rs = (hdr[Hdr::kRsoft] + 1e-3f) * (1.0f + 1e-6f) + 1e-3f;
       // the lattice's geometry (write_bound): half-side, 1 / h and the slack with the two 1e-3 of rs on top
       const bool lat = CAM && a.lattice != nullptr;
       float lat_half = 0.0f, lat_inv_h = 0.0f, lat_slack = 0.0f;
       if constexpr (CAM) {
         if (lat) {
-          const cf1_ptr lg = (cf1_ptr)(reinterpret_cast<const char*>(a.rec_buf) +
-                                       lattice_offset(a.Mpad / 2, (a.Mpad / 2 + 255) / 256));
-          lat_half = lg[4];
-          lat_inv_h = lg[5];
-          lat_slack = lg[6] + 2e-3f;
+          const cf1_ptr lg = (cf1_ptr)RecLayout::at<const char>(a.rec_buf, RecLayout(a.Mpad).lattice());
+          lat_half = lg[Lat::kHalf];
+          lat_inv_h = lg[Lat::kInvH];
+          lat_slack = lg[Lat::kSlack] + 2e-3f;
         }
       }
       float u = t;
@@ -627,8 +615,8 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       // code path (write_origins), when every lane of the wave has it (not NaN). Taken before
       // the loop so that D0 holds no register through the march.
       if (a.origin != nullptr && a.steps > 0 && !(SPLIT && a.cont_resume > 0)) {
-        const float D0 = a.origin[view];
-        rho_lb = a.origin[RM_MAX_VIEWS_PER_CALL + view];  // at the eye
+        const float D0 = a.origin[RecTail::kD0 + view];
+        rho_lb = a.origin[RecTail::kRhoLb + view];  // at the eye
         if (__all((__float_as_uint(D0) & 0x7fffffffu) <= 0x7f800000u)) {
           const float p[3] = {fmaf(d[0], t, o[0]), fmaf(d[1], t, o[1]), fmaf(d[2], t, o[2])};
           if (wave_escaped(0, p)) {
@@ -1081,9 +1069,9 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     float* rayf = rayf_all + wave * 64 * kFields;  // this wave's rays
     float* gta = L.slots + kWaves * 64 * kFields;  // [computing wave][source wave][64] g_t shares
     int* nsrc = reinterpret_cast<int*>(L.misc) + 40;  // [kWaves] the sources' ray counts (sweep 1, then 2)
-    const int np = a.Mpad / 2;
+    const RecLayout lay(a.Mpad);
     const float4* R4 = reinterpret_cast<const float4*>(a.rec_buf);
-    const float2* R2 = reinterpret_cast<const float2*>(R4 + 7 * (size_t)np);
+    const float2* R2 = reinterpret_cast<const float2*>(R4 + lay.p4_first());
     const int ngrp = (a.Mpad + 63) / 64;
     // The computing waves of a sweep: the block's source waves -- a set that does not depend on
     // which rayless waves left the march early, so the partition and every sum order are the same
@@ -1205,7 +1193,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
           const int grp = u / nsw1, kb = u - grp * nsw1, ke = min(u1 - grp * nsw1, nsw1);
           u = grp * nsw1 + ke;
           const int j = grp * 64 + lane;
-          const LaneSphere S = load_sphere<true>(R4, R2, np, j, a.Mpad);
+          const LaneSphere S = load_sphere<true>(R4, R2, lay, j, a.Mpad);
           const f2 GX = sp(S.gx), GY = sp(S.gy), GZ = sp(S.gz), CC = sp(S.cc), RR = sp(S.rr), CR = sp(S.cr), CG = sp(S.cg),
                    CB = sp(S.cbl), HX = sp(0.5f * S.gx), HY = sp(0.5f * S.gy), HZ = sp(0.5f * S.gz);
           f2 agc[3] = {sp(0.0f), sp(0.0f), sp(0.0f)}, agr = sp(0.0f), acol[3] = {sp(0.0f), sp(0.0f), sp(0.0f)};
@@ -1332,7 +1320,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
           const int grp = u / nsw2, kb = u - grp * nsw2, ke = min(u1 - grp * nsw2, nsw2);
           u = grp * nsw2 + ke;
           const int j = grp * 64 + lane;
-          const LaneSphere S = load_sphere<false>(R4, R2, np, j, a.Mpad);
+          const LaneSphere S = load_sphere<false>(R4, R2, lay, j, a.Mpad);
           const f2 GX = sp(S.gx), GY = sp(S.gy), GZ = sp(S.gz), CC = sp(S.cc), KR = sp(S.kr), HX = sp(0.5f * S.gx),
                    HY = sp(0.5f * S.gy), HZ = sp(0.5f * S.gz);
           f2 agc[3] = {sp(0.0f), sp(0.0f), sp(0.0f)}, agr = sp(0.0f);

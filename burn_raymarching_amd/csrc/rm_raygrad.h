@@ -55,20 +55,8 @@ __device__ __forceinline__ void camera_raw(const CamBasis& c, int x, int y, int 
 template <bool CAM>
 __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_raygrad_kernel(const KArgs a, const RayGradArgs r) {
   __shared__ float red[kWaves][kRgCols];
-  Lds L;
+  const Lds L = bind_records(a.rec_buf, a.Mpad);
   const int np = a.Mpad / 2;
-  L.P0 = (cf4_ptr)a.rec_buf;
-  L.P1 = L.P0 + np;
-  L.P2 = L.P1 + np;
-  L.P3 = L.P2 + np;
-  L.S0 = L.P3 + np;
-  L.S1 = L.S0 + np;
-  L.W = L.S1 + np;
-  L.P4 = (cf2_ptr)(L.W + np);
-  L.At = nullptr;
-  L.Wt = nullptr;
-  L.slots = nullptr;
-  L.misc = nullptr;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const long long npix = (long long)a.width * a.height;

@@ -1,6 +1,6 @@
 // rm_sdf.h -- the scene's distance field at points of the caller's choosing: rm_sdf_kernel<GRID, FULL>
 // (rm_sdf_query, rm_sdf_grid). Included by rm_kernels.hip inside namespace rm, after the record
-// accessors and packed helpers it shares with the other kernels.
+// accessors (rm_records.h) and packed helpers it shares with the other kernels.
 //
 // For a point p and every sphere j (scene.rs:60-79; the reference's expansion form of |p - c|^2
 // differs only in rounding):
@@ -36,7 +36,7 @@ struct SdfArgs {
   float* dist;   // nullable [n]
   float* grad;   // nullable [n,3]
   float* color;  // nullable [n,3]
-  const float* geom;  // rm_lattice_kernel: {origin x, y, z, spacing} in device memory (origin / spacing unused)
+  const float* geom;  // rm_lattice_kernel: the record buffer's lattice geometry (Lat; origin / spacing unused)
 };
 
 template <bool FULL>
@@ -118,20 +118,8 @@ __device__ __forceinline__ void sdf_sweep(const float p[3], const Lds& L, int np
 // the arguments -- the escape lattice's, which the record kernel forms (write_bound).
 template <bool GRID, bool FULL, bool DEV>
 __device__ __forceinline__ void sdf_body(const SdfArgs& a) {
-  Lds L;
+  const Lds L = bind_records(a.rec_buf, a.Mpad);
   const int np = a.Mpad / 2;
-  L.P0 = (cf4_ptr)a.rec_buf;
-  L.P1 = L.P0 + np;
-  L.P2 = L.P1 + np;
-  L.P3 = L.P2 + np;
-  L.S0 = L.P3 + np;
-  L.S1 = L.S0 + np;
-  L.W = L.S1 + np;
-  L.P4 = (cf2_ptr)(L.W + np);
-  L.At = nullptr;
-  L.Wt = nullptr;
-  L.slots = nullptr;
-  L.misc = nullptr;
 
   const long long idx = a.begin + (long long)blockIdx.x * kBlock + threadIdx.x;
   const bool valid = idx < a.n;
@@ -144,10 +132,10 @@ __device__ __forceinline__ void sdf_body(const SdfArgs& a) {
       const int iz = (int)(row / a.ny), iy = (int)(row - (long long)iz * a.ny);
       if constexpr (DEV) {
         const cf1_ptr g = (cf1_ptr)a.geom;
-        const float h = g[3];
-        p[0] = g[0] + (float)ix * h;
-        p[1] = g[1] + (float)iy * h;
-        p[2] = g[2] + (float)iz * h;
+        const float h = g[Lat::kH];
+        p[0] = g[Lat::kX0] + (float)ix * h;
+        p[1] = g[Lat::kY0] + (float)iy * h;
+        p[2] = g[Lat::kZ0] + (float)iz * h;
       } else {
         p[0] = a.origin[0] + (float)ix * a.spacing;
         p[1] = a.origin[1] + (float)iy * a.spacing;

@@ -1,6 +1,6 @@
 // rm_view.h -- the reference viewer's sphere-traced frame render (src/bin/viewer.rs +
 // src/bin/shader.wgsl), headless: rm_view_kernel (rm_view). Included by rm_kernels.hip inside
-// namespace rm, after the record accessors and packed helpers it shares with the other kernels.
+// namespace rm, after the record accessors (rm_records.h) and packed helpers it shares with the other kernels.
 //
 // The viewer's math is not the training render's (shader.wgsl:43-128):
 //   rays   ux = (2 (i + .5) / W - 1) W / H, uy = 1 - 2 (j + .5) / H, rd = normalize(ux uu + uy vv + focal ww)
@@ -153,21 +153,9 @@ __device__ __forceinline__ unsigned srgb8(float c) {
 
 __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_view_kernel(const ViewArgs a) {
   static_assert(kBlock == 256, "16x16 pixel tiles: four 8x8 waves");
-  Lds L;
+  const Lds L = bind_records(a.rec_buf, a.Mpad);
   const int np = a.Mpad / 2;
-  L.P0 = (cf4_ptr)a.rec_buf;
-  L.P1 = L.P0 + np;
-  L.P2 = L.P1 + np;
-  L.P3 = L.P2 + np;
-  L.S0 = L.P3 + np;
-  L.S1 = L.S0 + np;
-  L.W = L.S1 + np;
-  L.P4 = (cf2_ptr)(L.W + np);
-  L.At = nullptr;
-  L.Wt = nullptr;
-  L.slots = nullptr;
-  L.misc = nullptr;
-  const cf1_ptr hdr = (cf1_ptr)(L.P4 + np);  // {r_min, r_max, spread, 0, c0.x, c0.y, c0.z, R}
+  const cf1_ptr hdr = rec_header(L, a.Mpad);  // the bounding sphere (c0, R) of scene_bound
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tile = blockIdx.x, tile_y = tile / a.tiles_x, tile_x = tile - tile_y * a.tiles_x;
@@ -191,7 +179,7 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_view_kernel(const
   }
 
   const float nkappa = -a.kappa, inv_kappa = 1.0f / a.kappa;
-  const float c0[3] = {hdr[4], hdr[5], hdr[6]};
+  const float c0[3] = {hdr[Hdr::kCx], hdr[Hdr::kCy], hdr[Hdr::kCz]};
   const bool exits = a.skip_add > 0.0f;
   float rs2 = INFINITY;  // Rs'^2 of this launch's frame
   enum { kLive = 0, kHit = 1, kMiss = 2 };
@@ -199,7 +187,7 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_view_kernel(const
   if (exits) {
     const float oc[3] = {c0[0] - ro[0], c0[1] - ro[1], c0[2] - ro[2]};
     const float oc_len = sqrtf(fmaf(oc[2], oc[2], fmaf(oc[1], oc[1], oc[0] * oc[0])));
-    const float rs = fmaf(4e-6f, oc_len, (hdr[7] + a.skip_add) * (1.0f + 1e-5f));
+    const float rs = fmaf(4e-6f, oc_len, (hdr[Hdr::kR] + a.skip_add) * (1.0f + 1e-5f));
     rs2 = rs * rs;
     const float tca = fmaf(oc[2], rd[2], fmaf(oc[1], rd[1], oc[0] * rd[0]));
     const float pe[3] = {fmaf(-tca, rd[0], oc[0]), fmaf(-tca, rd[1], oc[1]), fmaf(-tca, rd[2], oc[2])};

@@ -38,6 +38,8 @@ def _plane_cams(sc, k):
     return [([g.c0[0] + 0.3, y, g.c0[2] + 2.5], [g.c0[0] - 0.5, y, g.c0[2]], 50.0)]
 
 
+TWO_BLOCK_CAM = ([0.0, 0.5, 2.5], [1.2, 0.5, 0.0], 40.0)
+
 FAR = np.array([29.0, -29.0, 29.0])  # 50.2 from the origin
 
 # name: (scene, cameras, (w, h), march steps, k)
@@ -52,6 +54,11 @@ CASES = {
     "one-centre": lambda: (coincident_scene(128), [([0.0, 0.3, 2.0], [0.6, 0.0, 0.0], 60.0)], (48, 80), 8, 5.0),
     "outliers-k5": lambda: (outlier_scene(300), [([0.0, 0.5, 3.5], [2.0, 0.5, 0.0], 40.0)], (64, 64), 32, 5.0),
     "lattice-plane": lambda: (outlier_scene(128), _plane_cams(outlier_scene(128), 32.0), (64, 64), 32, 32.0),
+    # 520 spheres: Mpad = 544, 272 pairs, two blocks of the record kernel -- the smallest scene whose record
+    # buffer has partial headers, so the lattice geometry (and every section behind the header) sits
+    # elsewhere than in the one-block cases above. The eye is "beside"'s, turned towards the cloud: at
+    # "beside" itself both proofs take all 60 waves.
+    "two-record-blocks": lambda: (cloud_scene(520), [TWO_BLOCK_CAM], (48, 80), 32, 32.0),
 }
 
 
@@ -118,6 +125,15 @@ def test_gap_scene_saves_more_and_exits_no_wave_that_shows(mods, runs, monkeypat
     waves_shown = sum(int(shown[v][wave_tiles(w, h)].any(1).sum()) for v in range(views))
     assert waves_shown > 0
     assert st_lat["waves_exited"] <= st_lat["waves"] - waves_shown
+
+
+def test_two_record_blocks_lattice_proves_strictly_more(mods, runs, monkeypatch):
+    """the 520-sphere case is not vacuous: test_escape_lattice_reference's CPU model (waves_taken) takes 55 of
+    this view's 60 waves with the lattice and 49 with the soft ball alone, so a kernel that read the lattice
+    geometry from the wrong offset cannot pass by proving nothing"""
+    res = runs("two-record-blocks", monkeypatch)[0]
+    st_lat, st_ball = res["lattice"][1], res["ball"][1]
+    assert st_lat["steps_saved"] > st_ball["steps_saved"]
 
 
 def test_inside_the_cloud_the_counters_are_the_soft_balls(mods, runs, monkeypatch):

@@ -37,7 +37,7 @@ def synthetic(m, seed):
 
 
 # name -> (scene, k, steps, width, height, cameras): the array-mode cases take the rays of the
-# listed cameras (C8: plus one ray, 577 in all)
+# listed cameras (C8, C10: plus one ray, 577 and 257 in all)
 CASES = {
     "C1": (final1_scene, 32.0, 40, 24, 24, [1]),
     "C2": (final1_scene, 5.0, 16, 24, 24, [9]),
@@ -48,9 +48,12 @@ CASES = {
     "C7": (lambda: synthetic(300, 9), 32.0, 16, 20, 24, [1]),  # several 64-sphere groups, above 256
     "C8": (final1_scene, 32.0, 40, 24, 24, [1]),             # array mode, 577 rays: partial wave and block
     "C9": (final1_scene, 32.0, 40, 20, 24, [1, 3, 5]),       # view boundaries inside 256-ray blocks (row order)
+    # 520 spheres: 272 pairs, two blocks of the record kernel (partial headers in the record buffer); array
+    # mode 257 rays (one 16x16 view plus one ray)
+    "C10": (lambda: synthetic(520, 10), 32.0, 16, 16, 16, [1]),
 }
-RAY_CASES = ["C1", "C2", "C3", "C4", "C5", "C6", "C7", "C8"]
-CAM_CASES = ["C1", "C2", "C3", "C4", "C7", "C9"]
+RAY_CASES = ["C1", "C2", "C3", "C4", "C5", "C6", "C7", "C8", "C10"]
+CAM_CASES = ["C1", "C2", "C3", "C4", "C7", "C9", "C10"]
 
 
 @pytest.fixture(scope="module")
@@ -93,7 +96,7 @@ def case(oracle, name):
         os_.append(o)
         ds_.append(d)
     o, d = np.concatenate(os_), np.concatenate(ds_)
-    if name == "C8":
+    if name in ("C8", "C10"):
         o, d = np.concatenate([o, o[100:101]]), np.concatenate([d, d[100:101]])
     gout = np.random.default_rng(sum(map(ord, name))).standard_normal(o.shape).astype(np.float32)
     ref_o, ref_d = rr.ray_grads(o, d, sc, k, steps, gout)

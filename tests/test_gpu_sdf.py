@@ -43,6 +43,9 @@ def _one():
 
 
 SCENES = {"golden": final1_scene, "one": _one, "m33": lambda: _synthetic(33, 3), "m300": lambda: _synthetic(300, 4)}
+# 520 spheres: 272 pairs, two blocks of the record kernel -- the smallest scene whose record buffer has
+# partial headers (test_two_record_blocks)
+TWO_BLOCKS = {"m520": lambda: _synthetic(520, 5)}
 _CACHE = {}
 
 
@@ -51,7 +54,7 @@ def pool(name):
     exactly the centre of sphere 0 (the clamp, the dropped gradient term), a point on its surface,
     NFAR points 1e3 units away, then uniform points in [-1, 1]^3."""
     if name not in _CACHE:
-        sc = SCENES[name]()
+        sc = {**SCENES, **TWO_BLOCKS}[name]()
         rng = np.random.default_rng(18)
         c0, r0 = sc["centers"][0].astype(np.float32), np.float32(sc["radius"][0])
         u = rng.normal(size=(1 + NFAR, 3))
@@ -128,6 +131,36 @@ def test_grid_equals_query_bit_for_bit(rm, name):
     qd, qc = render.sdf_query(torch.from_numpy(pts).cuda(), scene, K, color_sharpness=CSHARP, grad=False)
     assert bits(gd) == bits(qd) and bits(gc) == bits(qc)
     assert bits(render.sdf_grid(origin, spacing, shape, scene, K)) == bits(gd)  # the distance-only instance
+
+
+def test_two_record_blocks(rm):
+    """M = 520: sdf_query at the pool's first 257 points and sdf_grid on a 5x4x3 lattice, against the fp64
+    restatement under the file's bound (8 times the restatement's own fp32 error over the scene's pool,
+    near points). The lattice's points are not the pool's, so the restatement's fp32 run is first held to
+    that bound at them."""
+    render, _, _ = rm
+    sc, pts, far, ref64, ref32 = pool("m520")
+    near = ~far
+    bounds = {what: 8.0 * err(r32, r64, near) for what, r32, r64 in zip(("dist", "grad", "color"), ref32, ref64)}
+    n = 257
+    d, g, col = render.sdf_query(torch.from_numpy(pts[:n].copy()).cuda(), scene_t(sc), K, color_sharpness=CSHARP)
+    for what, a, r64 in zip(("dist", "grad", "color"), (d, g, col), ref64):
+        e = err(a.cpu().numpy(), r64[:n], near[:n])
+        print(f"sdf parity m520 N={n} near {what}: gpu {e:.3e} bound {bounds[what]:.3e}")
+        record_margin(f"sdf_{what}_near_m520_{n}", e, bounds[what])
+        assert np.isfinite(a.cpu().numpy()).all() and e <= bounds[what], (what, e, bounds[what])
+    origin, spacing, shape = (-0.5, -0.4, -0.3), 0.25, (5, 4, 3)
+    lat = S.lattice(origin, spacing, shape).reshape(-1, 3)
+    l64, l32 = S.field(lat, sc, K, CSHARP, torch.float64), S.field(lat, sc, K, CSHARP, torch.float32)
+    every = np.ones(len(lat), bool)
+    gd, gc = render.sdf_grid(origin, spacing, shape, scene_t(sc), K, color_sharpness=CSHARP, color=True)
+    assert tuple(gd.shape) == (3, 4, 5) and tuple(gc.shape) == (3, 4, 5, 3)
+    for what, a, i in (("dist", gd.reshape(-1), 0), ("color", gc.reshape(-1, 3), 2)):
+        e32, e = err(l32[i], l64[i], every), err(a.cpu().numpy(), l64[i], every)
+        print(f"sdf grid m520 {what}: gpu {e:.3e} fp32 {e32:.3e} bound {bounds[what]:.3e}")
+        record_margin(f"sdf_grid_{what}_m520", e, bounds[what])
+        assert e32 <= bounds[what], ("the reference's fp32 run", what, e32, bounds[what])
+        assert e <= bounds[what], (what, e, bounds[what])
 
 
 def test_fp16_colours(rm):

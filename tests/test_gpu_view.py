@@ -1,7 +1,7 @@
 """GPU tests of the viewer's frame render (rm_view, render.view, `rm_train view`) against the fp64
 numpy restatement (tests/view_ref.py), at the smallest shapes that can still go wrong: frames ragged
-in both tile dimensions, M = 1, odd pair padding (33), several record chunks (300), several frames
-per call and more frames than one launch carries.
+in both tile dimensions, M = 1, odd pair padding (33), several record chunks (300), two blocks of the
+record kernel (520), several frames per call and more frames than one launch carries.
 
 Parity. The bound is the project's forward bound: on the pixels where the GPU and
 fp64 agree on hit/miss, linear RGB max <= 1e-3 and mean <= 1e-5, depth within 1e-4. A pixel that
@@ -29,9 +29,11 @@ AWAY = ((0.0, 0.0, -2.5), -math.pi / 2, 0.0)              # looks away: every pi
 INSIDE = (tuple(float(x) for x in GOLD["centers"][0]), 1.0, 0.2)  # inside sphere 0: hit at t = 0
 FAR = ((0.0, 0.0, -6.0), math.pi / 2, 0.0)                # 6 units out: the reference viewer is black here
 
-# (name, scene, width, height, poses): the issue's cases, then M = 1 and the 70x45 three-pose call
+# (name, scene, width, height, poses): the issue's cases, then M = 1, the 70x45 three-pose call and M = 520
 CASES = V.parity_cases(GOLD) + [("one_sphere_40x24", ONE, 40, 24, [V.POSES[0], V.POSES[1]]),
-                                ("golden_70x45_special", GOLD, 70, 45, [AWAY, INSIDE, FAR, V.POSES[2]])]
+                                ("golden_70x45_special", GOLD, 70, 45, [AWAY, INSIDE, FAR, V.POSES[2]]),
+                                # 272 pairs: two blocks of the record kernel (partial headers in the record buffer)
+                                ("synth_M520_32x24", V.synthetic_scene(520, 5), 32, 24, [V.POSES[1]])]
 RGB_MAX, RGB_MEAN, DEPTH_TOL, EXCLUDED_CAP = 1e-3, 1e-5, 1e-4, 0.005
 
 
@@ -113,7 +115,8 @@ def test_two_calls_give_equal_bits(rm):
         assert x.tobytes() == y.tobytes()
 
 
-@pytest.mark.parametrize("case", ["golden_70x45_special", "synth_M300_s1", "golden_64x48", "one_sphere_40x24"])
+@pytest.mark.parametrize("case", ["golden_70x45_special", "synth_M300_s1", "golden_64x48", "one_sphere_40x24",
+                                  "synth_M520_32x24"])
 def test_exact_skip_changes_no_bit(rm, case):
     render, native = rm
     name, scene, w, h, poses = next(c for c in CASES if c[0] == case)
