@@ -723,6 +723,29 @@ int rm_sdf_query(rm_context* ctx, const float* points, int64_t num_points, const
   return run_sdf(ctx, false, points, num_points, nullptr, 0.0f, 0, 0, scene, sp, dist, grad, color);
 }
 
+int rm_sdf_query_backward(rm_context* ctx, const float* points, int64_t num_points, const rm_scene* scene,
+                          const rm_sdf_params* params, const float* grad_dist, const float* grad_color,
+                          const rm_grads* grads, float* grad_points, int32_t accumulate) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  rm_sdf_params sp;
+  int rc;
+  if ((rc = check_sdf_params(ctx, params, sp)) != RM_OK) return rc;
+  if (num_points < 0) return fail(ctx, RM_ERR_INVALID_ARG, "num_points %lld < 0", (long long)num_points);
+  if (!grad_dist && !grad_color) return fail(ctx, RM_ERR_INVALID_ARG, "grad_dist and grad_color are both NULL");
+  // the field does not depend on the light: those two members are never written
+  rm_grads want{};
+  if (grads) {
+    want.centers = grads->centers;
+    want.colors = grads->colors;
+    want.radius = grads->radius;
+  }
+  const bool scene_grad = want.centers || want.colors || want.radius;
+  if (!scene_grad && !grad_points) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
+  if (num_points > 0 && !points) return fail(ctx, RM_ERR_INVALID_ARG, "points is NULL");
+  return run_sdf_grad(ctx, points, num_points, scene, sp, grad_dist, grad_color, scene_grad ? &want : nullptr,
+                      grad_points, accumulate);
+}
+
 int rm_sdf_grid(rm_context* ctx, const float origin[3], float spacing, int32_t nx, int32_t ny, int32_t nz,
                 const rm_scene* scene, const rm_sdf_params* params, float* dist, float* color) {
   if (!ctx) return RM_ERR_INVALID_ARG;

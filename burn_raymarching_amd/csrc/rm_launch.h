@@ -1,7 +1,7 @@
 // rm_launch.h -- launch orchestration behind the C ABI: what a call is (Geometry, Call,
 // RayGradCall), its checks and its KArgs, and the launch sequences of the general kernel (run),
 // the small-scene kernel (run_small), the ray-gradient kernel (run_raygrad), the viewer's frame
-// render (run_view), the distance-field query (run_sdf) and the gradient reduction. Host code only; included by rm_kernels.hip after rm_context.h.
+// render (run_view), the distance-field query (run_sdf), its backward (run_sdf_grad) and the gradient reduction. Host code only; included by rm_kernels.hip after rm_context.h.
 #pragma once
 
 namespace {
@@ -1192,6 +1192,75 @@ int run_sdf(rm_context* ctx, bool grid, const float* points, long long n, const 
     else if (full) hipExtLaunchKernelGGL((rm_sdf_kernel<false, true>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, s);
     else hipExtLaunchKernelGGL((rm_sdf_kernel<false, false>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, s);
     RM_HIP(ctx, hipGetLastError());
+    done += nb * kBlock;
+  }
+  return RM_OK;
+}
+
+// ---- the distance field's backward (rm_sdf_grad_kernel, rm_sdf.h) ---------------------------------
+
+// Blocks of 256 points per launch: the sub-launch limit, and no more than keep the per-sphere part of
+// the launch's partial records within kSdfGradScratch bytes of the workspace (a record is 128 KB at
+// 4096 spheres: 2048 blocks).
+constexpr size_t kSdfGradScratch = (size_t)256 << 20;
+long long sdf_grad_blocks_per_launch(int Mpad) {
+  const long long fit = (long long)(kSdfGradScratch / (sizeof(float) * 8 * (size_t)Mpad));
+  return std::max<long long>(1, std::min<long long>(fit, max_blocks_per_launch()));
+}
+
+// rm_sdf_query_backward. want: the scene gradient's members to write (light_dir and ambient NULL), or
+// NULL for the point gradient alone. The partial records and the reduction's segment sums live in the
+// context's workspace, as the ray kernels' do; rm_reduce_partials and the finalize run unchanged on them.
+int run_sdf_grad(rm_context* ctx, const float* points, long long n, const rm_scene* scene, const rm_sdf_params& sp,
+                 const float* g_dist, const float* g_color, const rm_grads* want, float* g_points, int accumulate) {
+  ctx->opt_prepared = false;
+  int rc;
+  rm_march m;
+  rm_march_default(&m);
+  m.smooth_k = sp.smooth_k;
+  m.color_sharpness = sp.color_sharpness;
+  m.flags = sp.flags;
+  KArgs a;
+  if ((rc = scene_records(ctx, scene, false, m, n != 0, a)) != RM_OK) return rc;
+  if (n == 0 && (want == nullptr || accumulate)) return RM_OK;
+  m.mask_sharpness = 0.0f;
+  m.flags &= RM_MARCH_COLOR_F16;
+  Call c(kBwd, ray_geometry(nullptr, nullptr, 0, scene, &m));
+  if (n == 0) fill_scene_args(c, a);  // no records: the reduction needs M and the record size only
+  c.grads = want;
+  c.accumulate = accumulate;
+  const long long per = sdf_grad_blocks_per_launch(a.Mpad);
+  if (want != nullptr) {
+    const long long nbmax = std::max<long long>(1, std::min<long long>((n + kBlock - 1) / kBlock, per));
+    const size_t need = (size_t)(nbmax * a.rec + (long long)reduce_segs(nbmax) * a.rec + 4096) * sizeof(float);
+    if ((rc = ctx->ws.ensure(ctx, need, "workspace")) != RM_OK) return rc;
+    a.partials = ctx->ws.as<float>();
+  }
+  if (n == 0) return reduce_and_finalize(ctx, c, a, 0, true);  // every requested element: zero
+
+  SdfGradArgs s;
+  std::memset(&s, 0, sizeof s);
+  s.rec_buf = a.rec_buf;
+  s.Mpad = a.Mpad;
+  s.kappa = sp.smooth_k * kLog2e;
+  s.c10l = a.csharp * kLog2e;
+  s.cs = a.csharp;
+  s.points = points;
+  s.n = n;
+  s.g_dist = g_dist;
+  s.g_color = g_color;
+  s.g_points = g_points;
+  s.accumulate = accumulate ? 1 : 0;
+  s.partials = a.partials;
+  s.rec = a.rec;
+  for (long long done = 0; done < n;) {
+    const long long nb = std::min<long long>((n - done + kBlock - 1) / kBlock, per);
+    s.begin = done;
+    hipEvent_t ev0, ev1;
+    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
+    hipExtLaunchKernelGGL(rm_sdf_grad_kernel, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream, ev0, ev1, 0u, s);
+    RM_HIP(ctx, hipGetLastError());
+    if (want != nullptr && (rc = reduce_and_finalize(ctx, c, a, nb, done == 0)) != RM_OK) return rc;
     done += nb * kBlock;
   }
   return RM_OK;

@@ -1,5 +1,6 @@
 // rm_sdf.h -- the scene's distance field at points of the caller's choosing: rm_sdf_kernel<GRID, FULL>
-// (rm_sdf_query, rm_sdf_grid). Included by rm_kernels.hip inside namespace rm, after the record
+// (rm_sdf_query, rm_sdf_grid) and, at the end of the file, its backward rm_sdf_grad_kernel
+// (rm_sdf_query_backward). Included by rm_kernels.hip inside namespace rm, after the record
 // accessors (rm_records.h) and packed helpers it shares with the other kernels.
 //
 // For a point p and every sphere j (scene.rs:60-79; the reference's expansion form of |p - c|^2
@@ -176,4 +177,192 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_sdf_kernel(const 
 // sweep above, bit for bit, at the cell centres write_bound laid out for this call's scene.
 __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_lattice_kernel(const SdfArgs a) {
   sdf_body<true, false, true>(a);
+}
+
+// ---- the field's backward: rm_sdf_grad_kernel (rm_sdf_query_backward) -------------------------
+// Upstream gD_i (a scalar per point) and gC_i (three per point), either possibly absent. With e_j, q_j,
+// rho_j, d_j, beta, w and C = sum_j w_j col_j as above, per point
+//   a_j = gD beta_j - cs w_j (gC . (col_j - C)),   u_j = e_j / rho_j if q_j >= 1e-6, else 0
+//   dL/dc_j += -a_j u_j,  dL/dr_j += -a_j,  dL/dcol_j += w_j gC,  dL/dp_i = sum_j a_j u_j
+// (cs = color_sharpness). The clamp max(sum, 1e-8) of the shifted log-sum-exp is never active -- the
+// nearest sphere's term is 1 -- so it has no branch here. One block takes 256 points, in three sweeps:
+//   1. forward: sdf_sweep<true>, one point per lane: d_min, s, Zw, C;
+//   2. points (only when grad_points is asked for): one point per lane again, sum_j a_j u_j -- a_j needs
+//      the finished C;
+//   3. spheres (only when a scene gradient is asked for), with the roles turned around: every lane parks
+//      its point's twelve values {p, d_min | gD / s, gC / Zw | C} in LDS, then a lane owns a sphere
+//      pair and runs over the points in index order, reading them at an address the lanes of a group
+//      share (an LDS broadcast). The seven sums of a sphere sit in the lane's registers: no cross-lane
+//      reduction, one plain addition chain. Scenes of fewer than 256 pairs deal the points out over
+//      G = 256 / lanes groups of lanes = pow2ceil(pairs) >= 16 lanes each (group g takes the points
+//      i = g mod G, in order); the groups' sums are added in group order through LDS. More than 256
+//      pairs: one pass of the points per 256 pairs.
+// The block's sums are one partial record in the per-ray kernels' layout ([Mpad][8] | 8 scalars, scalar
+// 7 the live flag; rm_reduce.h), which rm_reduce_partials and the finalize turn into rm_grads in a
+// fixed order: no atomics, two calls give the same bits. A point whose seeds are all zero writes exact
+// zeros and adds exact zeros; a block of such points writes its live flag 0 and its points' zeros and
+// leaves before the first sweep -- the bits of not skipping. d_j has the forward sweep's bits (the same
+// operations, contraction off), so no exponent is positive.
+struct SdfGradArgs {
+  const float4* rec_buf;
+  int Mpad;
+  float kappa, c10l;  // smooth_k log2(e), color_sharpness log2(e)
+  float cs;           // color_sharpness
+  const float* points;  // [n,3]
+  long long begin, n;   // first point of this launch, points in all
+  const float* g_dist;   // nullable [n]
+  const float* g_color;  // nullable [n,3]
+  float* g_points;       // nullable [n,3]
+  int accumulate;        // g_points += (the scene gradient's accumulate is the finalize's)
+  float* partials;       // nullable: one record of `rec` floats per block of this launch
+  long long rec;
+};
+
+constexpr int kSdfPark = 12;  // floats a point parks for the sphere sweep (three float4)
+constexpr int kSdfSums = 14;  // sums of a sphere pair: (gc.xyz, gr, gcol.rgb) x 2
+
+// a_j for a sphere pair at shifted distance dd = d_min - d (<= 0): A = gD / s, GZ = gC / Zw
+__device__ __forceinline__ f2 sdf_pair_a(f2 dd, f2 KA, f2 CL, f2 CS, f2 A, const f2 (&GZ)[3], const f2 (&CC)[3], f2 c0,
+                                         f2 c1, f2 c2, f2& w) {
+#pragma clang fp contract(off)
+  const f2 b = exp2v(dd * KA);
+  w = exp2v(dd * CL);
+  const f2 t = fma2(GZ[2], c2 - CC[2], fma2(GZ[1], c1 - CC[1], GZ[0] * (c0 - CC[0])));
+  return A * b - (CS * w) * t;
+}
+
+// sweep 2: dL/dp of one point, sum_j a_j u_j
+__device__ __forceinline__ void sdf_point_grad(const float p[3], const Lds& L, int npairs, float kappa, float c10l,
+                                               float cs, float dmin, float A, const float gz[3], const float c[3],
+                                               float (&gp)[3]) {
+#pragma clang fp contract(off)
+  const f2 PX = sp(p[0]), PY = sp(p[1]), PZ = sp(p[2]), HALF = sp(0.5f), KA = sp(kappa), CL = sp(c10l), CS = sp(cs);
+  const f2 DN = sp(dmin), AA = sp(A), GZ[3] = {sp(gz[0]), sp(gz[1]), sp(gz[2])}, CC[3] = {sp(c[0]), sp(c[1]), sp(c[2])};
+  f2 G[3] = {sp(0.0f), sp(0.0f), sp(0.0f)};
+#pragma unroll 4
+  for (int i = 0; i < npairs; ++i) {
+    const float4 P0 = L.p0(i), P1 = L.p1(i), R = L.p2(i), C3 = L.p3(i);
+    const float2 C4 = L.p4(i);
+    const f2 ex = fma2(HALF, lo(P0), PX), ey = fma2(HALF, hi(P0), PY), ez = fma2(HALF, lo(P1), PZ);
+    const f2 q = fma2(ez, ez, fma2(ey, ey, ex * ex));
+    const f2 qc = clamp_q(q);
+    const f2 d = sqrt2(qc) - hi(R);
+    const f2 r = rsq2(qc);
+    const f2 ir = f2{q.x >= 1e-6f ? r.x : 0.0f, q.y >= 1e-6f ? r.y : 0.0f};
+    f2 w;
+    const f2 aj = sdf_pair_a(DN - d, KA, CL, CS, AA, GZ, CC, lo(C3), hi(C3), f2{C4.x, C4.y}, w);
+    const f2 au = aj * ir;
+    G[0] = fma2(au, ex, G[0]);
+    G[1] = fma2(au, ey, G[1]);
+    G[2] = fma2(au, ez, G[2]);
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) gp[k] = G[k].x + G[k].y;
+}
+
+__global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_sdf_grad_kernel(const SdfGradArgs a) {
+  static_assert(kBlock == 256, "256 points, up to 256 sphere pairs a pass");
+  __shared__ float4 park[kBlock * kSdfPark / 4];
+  __shared__ float comb[kSdfSums * kBlock];
+  const Lds L = bind_records(a.rec_buf, a.Mpad);
+  const int np = a.Mpad / 2, tid = threadIdx.x;
+  const long long idx = a.begin + (long long)blockIdx.x * kBlock + tid;
+  const bool valid = idx < a.n;
+  float p[3] = {0.0f, 0.0f, 0.0f}, gD = 0.0f, gC[3] = {0.0f, 0.0f, 0.0f};  // a masked lane: the origin, no seed
+  if (valid) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) p[k] = a.points[3 * idx + k];
+    if (a.g_dist != nullptr) gD = a.g_dist[idx];
+    if (a.g_color != nullptr)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) gC[k] = a.g_color[3 * idx + k];
+  }
+  const bool seeded = gD != 0.0f || gC[0] != 0.0f || gC[1] != 0.0f || gC[2] != 0.0f;
+  const bool live = __syncthreads_or(seeded ? 1 : 0) != 0;
+  float* prow = a.partials != nullptr ? a.partials + (long long)blockIdx.x * a.rec : nullptr;
+  if (prow != nullptr && tid < 8) prow[(long long)a.Mpad * 8 + tid] = tid == 7 && live ? 1.0f : 0.0f;
+
+  float gp[3] = {0.0f, 0.0f, 0.0f};
+  if (live) {
+    float dmin, s, zw = 1.0f, g[3] = {0.0f, 0.0f, 0.0f}, col[3] = {0.0f, 0.0f, 0.0f};
+    sdf_sweep<true>(p, L, np, a.kappa, a.c10l, dmin, s, zw, g, col);
+    const float is = 1.0f / s, iz = 1.0f / zw;
+    const float A = gD * is, gz[3] = {gC[0] * iz, gC[1] * iz, gC[2] * iz}, c[3] = {col[0] * iz, col[1] * iz, col[2] * iz};
+    if (a.g_points != nullptr) sdf_point_grad(p, L, np, a.kappa, a.c10l, a.cs, dmin, A, gz, c, gp);
+    if (prow != nullptr) {
+#pragma clang fp contract(off)
+      park[3 * tid] = make_float4(p[0], p[1], p[2], dmin);
+      park[3 * tid + 1] = make_float4(A, gz[0], gz[1], gz[2]);
+      park[3 * tid + 2] = make_float4(c[0], c[1], c[2], 0.0f);
+      __syncthreads();
+      int lanes = 16;  // of a group: pow2ceil(pairs), 16 ... 256
+      while (lanes < np && lanes < kBlock) lanes *= 2;
+      const int groups = kBlock / lanes, li = tid & (lanes - 1), grp = tid / lanes;
+      const f2 HALF = sp(0.5f), KA = sp(a.kappa), CL = sp(a.c10l), CS = sp(a.cs);
+      const float2* P4 = reinterpret_cast<const float2*>(a.rec_buf + RecLayout(a.Mpad).p4_first());
+      for (int base = 0; base < np; base += kBlock) {
+        const int ip = base + li;
+        const bool own = ip < np;
+        const int ic = own ? ip : np - 1;
+        const RecLayout lay(a.Mpad);
+        const float4 P0 = a.rec_buf[lay.pair(RecLayout::kP0, ic)], P1 = a.rec_buf[lay.pair(RecLayout::kP1, ic)],
+                     R = a.rec_buf[lay.pair(RecLayout::kP2, ic)], C3 = a.rec_buf[lay.pair(RecLayout::kP3, ic)];
+        const float2 C4 = P4[ic];
+        const f2 c0 = lo(C3), c1 = hi(C3), c2 = f2{C4.x, C4.y}, rad = hi(R);
+        f2 S[7];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) S[k] = sp(0.0f);
+        for (int i = grp; i < kBlock; i += groups) {
+          const float4 v0 = park[3 * i], v1 = park[3 * i + 1], v2 = park[3 * i + 2];
+          const f2 ex = fma2(HALF, lo(P0), sp(v0.x)), ey = fma2(HALF, hi(P0), sp(v0.y)), ez = fma2(HALF, lo(P1), sp(v0.z));
+          const f2 q = fma2(ez, ez, fma2(ey, ey, ex * ex));
+          const f2 qc = clamp_q(q);
+          const f2 d = sqrt2(qc) - rad;
+          const f2 r = rsq2(qc);
+          const f2 ir = f2{q.x >= 1e-6f ? r.x : 0.0f, q.y >= 1e-6f ? r.y : 0.0f};
+          const f2 GZ[3] = {sp(v1.y), sp(v1.z), sp(v1.w)}, CC[3] = {sp(v2.x), sp(v2.y), sp(v2.z)};
+          f2 w;
+          const f2 aj = sdf_pair_a(sp(v0.w) - d, KA, CL, CS, sp(v1.x), GZ, CC, c0, c1, c2, w);
+          const f2 nau = -(aj * ir);
+          S[0] = fma2(nau, ex, S[0]);
+          S[1] = fma2(nau, ey, S[1]);
+          S[2] = fma2(nau, ez, S[2]);
+          S[3] = S[3] - aj;
+          S[4] = fma2(w, GZ[0], S[4]);
+          S[5] = fma2(w, GZ[1], S[5]);
+          S[6] = fma2(w, GZ[2], S[6]);
+        }
+        // the groups' sums, added in group order by the first group's lanes; sum k of sphere h at comb[2k + h]
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+          comb[(2 * k) * kBlock + tid] = S[k].x;
+          comb[(2 * k + 1) * kBlock + tid] = S[k].y;
+        }
+        __syncthreads();
+        if (grp == 0 && own) {
+          float t[kSdfSums];
+#pragma unroll
+          for (int k = 0; k < kSdfSums; ++k) {
+            float acc = comb[k * kBlock + li];
+            for (int gi = 1; gi < groups; ++gi) acc += comb[k * kBlock + gi * lanes + li];
+            t[k] = acc;
+          }
+          float4* dst = reinterpret_cast<float4*>(prow + (long long)ip * 16);  // spheres 2 ip, 2 ip + 1
+          dst[0] = make_float4(t[0], t[2], t[4], t[6]);
+          dst[1] = make_float4(t[8], t[10], t[12], 0.0f);
+          dst[2] = make_float4(t[1], t[3], t[5], t[7]);
+          dst[3] = make_float4(t[9], t[11], t[13], 0.0f);
+        }
+        __syncthreads();  // comb is free for the next pass
+      }
+    }
+  }
+  if (a.g_points != nullptr && valid) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float v = seeded ? gp[k] : 0.0f;
+      float* dst = a.g_points + 3 * idx + k;
+      *dst = a.accumulate ? *dst + v : v;
+    }
+  }
 }

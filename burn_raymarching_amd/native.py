@@ -110,6 +110,8 @@ SIGNATURES = {
                                ctypes.POINTER(RmViewParams), _P, _P, _P]),
     "rm_sdf_params_default": (None, [ctypes.POINTER(RmSdfParams)]),
     "rm_sdf_query": (ctypes.c_int, [_P, _P, _I64, ctypes.POINTER(RmScene), ctypes.POINTER(RmSdfParams), _P, _P, _P]),
+    "rm_sdf_query_backward": (ctypes.c_int, [_P, _P, _I64, ctypes.POINTER(RmScene), ctypes.POINTER(RmSdfParams), _P, _P,
+                                             ctypes.POINTER(RmGrads), _P, _I32]),
     "rm_sdf_grid": (ctypes.c_int, [_P, ctypes.POINTER(_F * 3), _F, _I32, _I32, _I32, ctypes.POINTER(RmScene),
                                    ctypes.POINTER(RmSdfParams), _P, _P]),
     "rm_gather_rays": (ctypes.c_int, [_P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P]),

@@ -16,7 +16,10 @@ Names and argument meaning follow the reference:
     viewer's frames (viewer.rs + shader.wgsl), headless: rm_view, not differentiable;
   * ``sdf_query(points, scene)`` / ``sdf_grid(origin, spacing, shape, scene)`` -- the scene's
     distance field (scene.rs:60-79), its gradient and blended colour at points of the caller's
-    choosing or on a lattice: rm_sdf_query / rm_sdf_grid.
+    choosing or on a lattice: rm_sdf_query / rm_sdf_grid;
+  * ``sdf_field(points, centers, colors, radius)`` -- the field's distance and colour as an
+    autograd function over the points and the scene (rm_sdf_query_backward; ``sdf_query_backward``
+    is the call itself).
 
 Tensors are torch CUDA (HIP) tensors, fp32, ``[N, 3]``; torch provides device memory
 and the stream only. Shapes are checked on the host before any launch.
@@ -548,7 +551,7 @@ def sdf_query(points, scene: Scene, smooth_k=32.0, *, color_sharpness=10.0, grad
     no term from a sphere whose centre the point sits on) and the blended colour [N, 3]
     (softmax(-color_sharpness d) over the spheres' colours, renderer_diff.rs:64-80). `scene` is used
     as given: add the training activation's 0.01 to scene.json's radii for the surface training
-    fitted. No autograd."""
+    fitted. No autograd: sdf_field is the differentiable form of dist and color."""
     n = points.shape[0]
     points = _f32(points, (n, 3), "points")
     dev = points.device
@@ -561,6 +564,101 @@ def sdf_query(points, scene: Scene, smooth_k=32.0, *, color_sharpness=10.0, grad
                                     _ptr(dist), _ptr(g), _ptr(col)), "rm_sdf_query")
     out = (dist,) + ((g,) if grad else ()) + ((col,) if color else ())
     return out[0] if len(out) == 1 else out
+
+
+def _field_scene(centers, colors, radius):
+    """rm_scene of a distance-field call: no light (the field does not read it). Returns the struct
+    and the tensors it points into, which the caller keeps alive until the call is made."""
+    m = centers.shape[0]
+    centers = _f32(centers, (m, 3), "centers")
+    half = colors.dtype == torch.float16
+    if half:
+        if not colors.is_cuda or tuple(colors.shape) != (m, 3):
+            raise ValueError("fp16 colors must be a [M,3] device tensor")
+        colors = colors.contiguous()
+    else:
+        colors = _f32(colors, (m, 3), "colors")
+    radius = _f32(radius.reshape(-1), (m,), "radius")
+    cs = RmScene(centers.data_ptr(), colors.data_ptr(), radius.data_ptr(), None, None, m)
+    return cs, (centers, colors, radius), native.RM_MARCH_COLOR_F16 if half else 0
+
+
+def sdf_query_backward(points, centers, colors, radius, smooth_k=32.0, *, color_sharpness=10.0, grad_dist=None,
+                       grad_color=None, want=("centers", "colors", "radius", "points")):
+    """The backward of the field's dist and color (rm_sdf_query_backward, one call): for upstream
+    gradients grad_dist [N] and / or grad_color [N, 3], the gradients named in `want` as a dict of
+    float32 tensors (centers [M, 3], colors [M, 3], radius [M], points [N, 3]). Half `colors` select
+    the fp16 path; their gradient is float32 all the same. Deterministic: two calls give the same
+    bits."""
+    n = points.shape[0]
+    points = _f32(points, (n, 3), "points")
+    dev = points.device
+    cs, keep, flags = _field_scene(centers, colors, radius)
+    m = cs.num_spheres
+    gd = _f32(grad_dist.reshape(-1), (n,), "grad_dist") if grad_dist is not None else None
+    gc = _f32(grad_color, (n, 3), "grad_color") if grad_color is not None else None
+    shapes = {"centers": (m, 3), "colors": (m, 3), "radius": (m,), "points": (n, 3)}
+    unknown = [k for k in want if k not in shapes]
+    if unknown:
+        raise ValueError(f"unknown gradient {unknown[0]!r}")
+    out = {k: torch.empty(shapes[k], device=dev) for k in want}
+    g = RmGrads(*[out[k].data_ptr() if k in out else None for k in ("centers", "colors", "radius")], None, None)
+    p = native.sdf_params(smooth_k=float(smooth_k), color_sharpness=float(color_sharpness), flags=flags)
+    ctx = context(dev)
+    ctx.check(ctx._lib.rm_sdf_query_backward(ctx.handle, _ptr(points), n, ctypes.byref(cs), ctypes.byref(p), _ptr(gd),
+                                             _ptr(gc), ctypes.byref(g), _ptr(out.get("points")), 0),
+              "rm_sdf_query_backward")
+    del keep
+    return out
+
+
+class _SdfFieldFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, centers, colors, radius, smooth_k, color_sharpness):
+        n = points.shape[0]
+        pts = _f32(points.detach(), (n, 3), "points")
+        cs, keep, flags = _field_scene(centers.detach(), colors.detach(), radius.detach())
+        dist = torch.empty((n,), device=pts.device)
+        col = torch.empty((n, 3), device=pts.device)
+        p = native.sdf_params(smooth_k=smooth_k, color_sharpness=color_sharpness, flags=flags)
+        c = context(pts.device)
+        c.check(c._lib.rm_sdf_query(c.handle, _ptr(pts), n, ctypes.byref(cs), ctypes.byref(p), _ptr(dist), None,
+                                    _ptr(col)), "rm_sdf_query")
+        ctx.save_for_backward(pts, *keep)
+        ctx.consts = (smooth_k, color_sharpness)
+        ctx.shapes = (points.shape, radius.shape)
+        ctx.set_materialize_grads(False)
+        return dist, col
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_dist, grad_color):
+        pts, centers, colors, radius = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want = [k for k, w in zip(("points", "centers", "colors", "radius"), need[:4]) if w]
+        if not want or (grad_dist is None and grad_color is None):
+            return (None,) * 6
+        g = sdf_query_backward(pts, centers, colors, radius, ctx.consts[0], color_sharpness=ctx.consts[1],
+                               grad_dist=grad_dist.contiguous().float() if grad_dist is not None else None,
+                               grad_color=grad_color.contiguous().float() if grad_color is not None else None, want=want)
+        gcol = g.get("colors")
+        if gcol is not None and colors.dtype == torch.float16:
+            gcol = gcol.half()
+        gr = g.get("radius")
+        return (g["points"].reshape(ctx.shapes[0]) if "points" in g else None, g.get("centers"), gcol,
+                gr.reshape(ctx.shapes[1]) if gr is not None else None, None, None)
+
+
+def sdf_field(points, centers, colors, radius, smooth_k=32.0, *, color_sharpness=10.0):
+    """The distance field as a differentiable function: (dist [N], color [N, 3]) of sdf_query at
+    `points` [N, 3] for the scene (centers [M, 3], colors [M, 3], radius [M]), with gradients for all
+    four through torch.autograd -- supervision in 3-D: fitting the spheres to a point cloud, pulling
+    the surface onto depth samples or coloured points, field regularisers, moving query points. The
+    forward is rm_sdf_query; the backward is one rm_sdf_query_backward call that computes only the
+    gradients whose inputs require grad, from the outputs that received one. Half-precision `colors`
+    select the fp16 path and receive their float32 gradient cast to half. First order only (no
+    gradient through sdf_query's grad output, no double backward)."""
+    return _SdfFieldFn.apply(points, centers, colors, radius, float(smooth_k), float(color_sharpness))
 
 
 def sdf_grid(origin, spacing, shape, scene: Scene, smooth_k=32.0, *, color_sharpness=10.0, color=False):

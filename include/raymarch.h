@@ -373,7 +373,30 @@ void rm_sdf_params_default(rm_sdf_params* params);   /* 32, 10, 0 */
  * defaults. */
 int rm_sdf_query(rm_context* ctx, const float* points, int64_t num_points, const rm_scene* scene,
                  const rm_sdf_params* params, float* dist, float* grad, float* color);
-/* The same on the lattice p = origin + (float)i * spacing per axis (formed in the kernel in fp32
+/* The backward of rm_sdf_query's dist and color (not of its grad: no second order). For upstream
+ * gradients gD = grad_dist [N] and gC = grad_color [N,3] (device; either may be NULL, not both), with
+ * e_j = p - c_j, q_j = |e_j|^2, rho_j = sqrt(max(q_j, 1e-6)), beta = softmax(-k d), w =
+ * softmax(-color_sharpness d) and C = sum_j w_j col_j as above, per point
+ *   a_j = gD beta_j - color_sharpness w_j (gC . (col_j - C)),
+ *   u_j = e_j / rho_j if q_j >= 1e-6, else 0 (the zero Jacobian of clamp_min, as in grad above),
+ *   dL/dc_j += -a_j u_j,  dL/dr_j += -a_j,  dL/dcol_j += w_j gC,  dL/dp_i = sum_j a_j u_j.
+ * The clamp_min(sum, 1e-8) of the shifted log-sum-exp is never active (the nearest sphere's term is
+ * 1) and has no branch in the gradient. Outputs: grads (nullable; its centers / colors / radius, any
+ * of them NULL to skip it; light_dir and ambient are never written: the field does not depend on
+ * them) and grad_points [N,3] (nullable); at least one output must be requested. accumulate != 0
+ * adds into the outputs; otherwise every element of every requested output is overwritten, all M
+ * rows of grads included. num_points == 0 with accumulate == 0 writes zeros to grads and returns
+ * without a per-point launch. params as in rm_sdf_query; with RM_MARCH_COLOR_F16 the scene's colours
+ * are read as binary16 and grads->colors stays float32. No floating-point atomics: every sum over
+ * the points is taken in a fixed order, two identical calls give identical bits, and an output's bits
+ * do not depend on which other outputs are requested. A point whose seeds are all zero contributes
+ * exact zeros. Calls of more points than one launch takes are split as the ray calls are. Scratch
+ * (one partial record of 8 M + 8 floats per 256 points of a launch, at most 256 MB of them, plus the
+ * reduction's segment sums) is the context's workspace, grown on demand: the first call may allocate. */
+int rm_sdf_query_backward(rm_context* ctx, const float* points, int64_t num_points, const rm_scene* scene,
+                          const rm_sdf_params* params, const float* grad_dist, const float* grad_color,
+                          const rm_grads* grads, float* grad_points, int32_t accumulate);
+/* rm_sdf_query on the lattice p = origin + (float)i * spacing per axis (formed in the kernel in fp32
  * with these two roundings, no fused multiply-add, so a host reproduces the points bit for bit; no
  * point array): origin is HOST memory, spacing > 0, nx, ny, nz >= 1. dist [nz,ny,nx] and color
  * [nz,ny,nx,3] (either NULL, not both), x fastest: index (iz ny + iy) nx + ix. Bit for bit
