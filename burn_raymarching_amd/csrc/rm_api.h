@@ -213,6 +213,15 @@ int rm_debug_block_trace(rm_context* ctx, unsigned long long* host, int64_t cap_
 }
 #endif
 
+int rm_debug_tile_proof(rm_context* ctx, uint8_t* host, int64_t capacity, int64_t* n_waves) {
+  if (!ctx || !host || !n_waves || capacity < 0) return RM_ERR_INVALID_ARG;
+  RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const long long n = ctx->tile_proof ? std::min<long long>(ctx->tile_proof_n, capacity) : 0;
+  *n_waves = n;
+  if (n > 0) RM_HIP(ctx, hipMemcpy(host, ctx->tile_proof.p, (size_t)n, hipMemcpyDeviceToHost));
+  return RM_OK;
+}
+
 int rm_debug_stall(rm_context* ctx, int32_t max_ms) {
   if (!ctx) return RM_ERR_INVALID_ARG;
   if (max_ms < 1 || max_ms > 600000) return fail(ctx, RM_ERR_INVALID_ARG, "max_ms %d out of [1, 600000]", max_ms);
@@ -313,7 +322,8 @@ int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres) {
     if ((rc = ctx->rec.ensure(ctx, RecLayout(pad_spheres(max_spheres)).bytes(), "record buffer")) != RM_OK) return rc;
   }
   if (rays >= kLatticeMinRays && pad_spheres(max_spheres) >= kProofMinSpheres &&
-      (rc = ctx->lattice.ensure(ctx, sizeof(float) * kLatticeCells, "escape lattice")) != RM_OK)
+      ((rc = ctx->lattice.ensure(ctx, sizeof(float) * kLatticeCells, "escape lattice")) != RM_OK ||
+       (rc = ctx->tile_proof.ensure(ctx, (size_t)kMaxBlocksPerLaunch * kWaves, "tile proof")) != RM_OK))
     return rc;
   return ctx->ws.ensure(ctx, ws_need(rays, max_spheres), "workspace");
 }

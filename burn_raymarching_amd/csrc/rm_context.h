@@ -54,6 +54,8 @@ struct rm_context {
   DevBuf stats_dev;     // work counters (rm_stats_enable), kStatsWords words
   DevBuf esc_flags;     // per-block escape flags, kMaxBlocksPerLaunch ints
   DevBuf lattice;       // the current call's escape lattice, kLatticeN^3 floats (rm_lattice_kernel)
+  DevBuf tile_proof;    // the current launch's tile-proof bytes, one per wave (rm_tile_proof_kernel)
+  long long tile_proof_n = 0;  // bytes the last launch with the tile proof wrote (rm_debug_tile_proof)
   DevBuf arrivals;      // rm_small_kernel's arrival counter (zero between launches)
   DevBuf red_arrivals;  // rm_reduce_partials' per-column-block arrival counters
   DevBuf opt_arrival;   // rm_train_step_camera_adam: the reduction's column-block counter

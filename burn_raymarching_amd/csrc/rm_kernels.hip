@@ -105,7 +105,7 @@ struct KArgs {
   float gone_d;               // > 0: rays that provably escape past this distance are `gone` (see the march)
   int early_exit;             // waves whose rays are all gone stop marching
   int proof;                  // the escape proof before the march (rm_ray_kernel<.., PROOF>; march_policy): 1 the
-                              // soft ball alone, 2 with the call's lattice
+                              // soft ball alone, 2 with the call's lattice (the tile proof before the launch, or per ray in bound_proof)
   int split;                  // split march (RM_MARCH_SPLIT): kSplitRays rays per block, a quarter of the spheres per wave
   int mfma;                   // march sums on the matrix cores (lse_mfma) instead of lse_weighted
   int shift_max;              // RM_MARCH_FORCE_MAX_SHIFT: every march step takes the running-max shift
@@ -183,6 +183,9 @@ struct KArgs {
   // nullable: the call's escape lattice, kLatticeN^3 cell-centre soft-min values (proof == 2;
   // rm_lattice_kernel). Last, so that the kernels that never read it see the arguments where they were.
   const float* lattice;
+  // nullable: one byte per wave of this launch (logical block * kWaves + wave), 1 where rm_tile_proof_kernel
+  // proved every ray of the wave gone from the lattice (proof == 2, the launches tile_proof_policy picks)
+  const unsigned char* tile_proof;
 #ifdef RM_BLOCK_TRACE
   unsigned long long* btrace;  // measurement build: per-wave timing records (rm_ray_kernel)
 #endif

@@ -398,7 +398,7 @@ int prepare_records(rm_context* ctx, KArgs& a, bool origin) {
   return RM_OK;
 }
 
-// The call's escape lattice (KArgs::lattice; bound_proof in rm_ray_kernel): the soft-min at the
+// The call's escape lattice (KArgs::lattice; rm_tile_proof_kernel or bound_proof reads it): the soft-min at the
 // kLatticeN^3 cell centres the record kernel laid out, by the distance-only lattice sweep of
 // rm_sdf_grid. Once per call, after the record kernels and before the per-ray launches, on the call's
 // stream: the scene changes with every optimizer step, so nothing of it is kept across calls.
@@ -417,6 +417,37 @@ int fill_lattice(rm_context* ctx, const KArgs& a) {
   static_assert(kLatticeCells % kBlock == 0 && kLatticeCells / kBlock <= kMaxBlocksPerLaunch, "one launch");
   hipLaunchKernelGGL(rm_lattice_kernel, dim3((unsigned)(kLatticeCells / kBlock)), dim3(kBlock), 0, ctx->stream, s);
   RM_HIP(ctx, hipGetLastError());
+  return RM_OK;
+}
+
+// Where a launch of a call with the lattice reads it: in the tile proof before the launch (true) or per ray
+// inside bound_proof (false; rm_ray.h). The tile proof needs the 16x16 tiling -- in rows order a wave's 64
+// rays are no pixel rectangle and have no narrow cone -- and a launch large enough to pay for it: one lane per
+// tile, each a chain of up to `steps` dependent bound steps of about 0.4 us, it takes 26 us at 10 views of
+// 512x512 and 32 steps however few tiles there are, and 42 us at 80 views. Measured against the per-ray lookup
+// (profiles/r20_tile_proof_ab.txt): 80 views +3.8 %, 10 views a tie at 32 steps and -0.6 to -0.9 % at 64
+// steps. Launches below kTileProofMinRays rays (20 views of 512x512) keep the per-ray lookup; env
+// RM_PROOF_LATTICE=1 takes the tile proof at any size. Either way the same waves' results: what a proof
+// tries changes none.
+constexpr long long kTileProofMinRays = 5242880;
+bool tile_proof_policy(const KArgs& a, long long nr) {
+  return a.lattice != nullptr && a.tiling == 2 && (nr >= kTileProofMinRays || env_is("RM_PROOF_LATTICE", '1'));
+}
+
+// The tile proof of one per-ray launch of a call with the lattice (KArgs::tile_proof; rm_tile_proof_kernel):
+// a byte per wave of the launch's nb blocks, written on the call's stream after the lattice and the origin
+// kernel and before the per-ray launch, which reads it. Nothing of it is kept: every launch writes all of its
+// bytes, inside a captured graph as outside.
+int tile_proof(rm_context* ctx, KArgs& a, long long nb) {
+  int rc;
+  if ((rc = ctx->tile_proof.ensure(ctx, (size_t)kMaxBlocksPerLaunch * kWaves, "tile proof")) != RM_OK) return rc;
+  unsigned char* taken = ctx->tile_proof.as<unsigned char>();
+  const long long n_tiles = nb * kWaves;
+  hipLaunchKernelGGL(rm_tile_proof_kernel, dim3((unsigned)((n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
+                     a, taken, n_tiles);
+  RM_HIP(ctx, hipGetLastError());
+  ctx->tile_proof_n = n_tiles;
+  a.tile_proof = taken;
   return RM_OK;
 }
 
@@ -978,6 +1009,9 @@ int run(rm_context* ctx, const Call& c) {
       RM_HIP(ctx, hipGetLastError());
       a.esc_flags = flags;
     }
+    a.tile_proof = nullptr;
+    ctx->tile_proof_n = 0;  // rm_debug_tile_proof: a launch without the tile proof leaves no bytes
+    if (l.nb > 0 && tile_proof_policy(a, l.nr) && (rc = tile_proof(ctx, a, l.nb)) != RM_OK) return rc;
     if (l.nb > 0) {
 #ifdef RM_BLOCK_TRACE
       if ((rc = bind_block_trace(ctx, a, l.nb * kWaves)) != RM_OK) return rc;

@@ -539,12 +539,20 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // below 256 x 6e-8 each, 1e-4 in all. A wave gives up once a ray's bound step falls to
     // kProofMinStep (not to 0: a ray creeping along the ball is not proven in the steps left either,
     // tools/escape_proof_sim.py): what the proof tries changes no result.
-    // Camera mode with the call's lattice (KArgs::lattice, march_policy): L = max(|p - c_0| - R_soft, G[cell] - slack)
+    // Camera mode with the call's lattice (KArgs::lattice, march_policy). The soft ball needs spheres out of
+    // the way in every direction; the lattice sees the gaps between them (once the optimizer has thrown a few
+    // spheres outwards, R_soft covers all the rays thread through: profiles/r19_escape_lattice_sim.txt). It
+    // enters in one of two places, the host's choice per launch (tile_proof_policy, rm_launch.h):
+    // (a) Before this launch (KArgs::tile_proof bound). rm_tile_proof_kernel (rm_sdf.h) marches one bound
+    // trajectory per wave tile, stepping by the larger of the soft ball and the lattice's bound, and leaves a
+    // byte per wave: 1, every ray of the wave is proven gone, and the wave stops here, booking what
+    // bound_proof books; 0, not known, and the wave runs bound_proof below, the soft ball alone -- the waves
+    // taken are a superset of the soft ball's, and the lookup below is skipped by a wave-uniform branch.
+    // (b) Here, per ray (KArgs::tile_proof null: rows order, where a wave is no pixel rectangle, and launches
+    // too small to hide the pre-pass's chain): L = max(|p - c_0| - R_soft, G[cell] - slack)
     // inside the lattice's cube, the soft ball alone outside it. G[cell] is the soft-min at the cell's centre
     // x_c (rm_lattice_kernel) and D is 1-Lipschitz, so D(p) >= D(x_c) - |p - x_c|: a point of the cell is at
-    // most the half-diagonal h sqrt(3)/2 from x_c. The soft ball needs spheres out of the way in every
-    // direction; the lattice sees the gaps between them (once the optimizer has thrown a few spheres
-    // outwards, R_soft covers all the rays thread through: profiles/r19_escape_lattice_sim.txt).
+    // most the half-diagonal h sqrt(3)/2 from x_c.
     // Margins: slack = h sqrt(3)/2 (1 + 1e-4) + 1e-3 (write_bound), and the two 1e-3 of the soft ball on top (the
     // march's and the bound step's). The 1e-4 relative covers the cell index: (e + half) / h is formed with
     // three roundings, below 3e-7 N cells in all, so a point rounded into a neighbouring cell is within
@@ -554,14 +562,13 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // below 2 B) and its logarithm (1e-6 / kappa). The maximum of two lower bounds is a lower bound; the
     // give-up rule, the votes and steps_saved are the soft ball's. Array mode keeps the soft ball alone.
     static_assert((kLatticeN & (kLatticeN - 1)) == 0, "the inside test takes a power of two");
-    constexpr float kProofMinStep = 0.02f;
     auto bound_proof = [&](int st) {
       // a wave vote: origins differ per lane (array mode; a wave across two views), and every lane
       // takes part in the votes below and must leave with the same answer (dead is wave-uniform)
       if (__any(!(onorm + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= 256.0f))) return false;
       const float rs = (hdr[Hdr::kRsoft] + 1e-3f) * (1.0f + 1e-6f) + 1e-3f;
       // the lattice's geometry (write_bound): half-side, 1 / h and the slack with the two 1e-3 of rs on top
-      const bool lat = CAM && a.lattice != nullptr;
+      const bool lat = CAM && a.lattice != nullptr && a.tile_proof == nullptr;
       float lat_half = 0.0f, lat_inv_h = 0.0f, lat_slack = 0.0f;
       if constexpr (CAM) {
         if (lat) {
@@ -657,7 +664,16 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
       st0 = a.cont_resume;
     }
     if constexpr (PROOF) {  // the host's choice (march_policy): exit on, no debug output, kProofMinSpheres
-      if (!dead && bound_proof(st0)) dead = true;
+      bool taken = false;  // wave-uniform: the tile proof's byte of this wave (a scalar load)
+      if constexpr (CAM) {
+        if (!dead && a.tile_proof != nullptr) taken = a.tile_proof[blk * kWaves + wave] != 0;
+      }
+      if (taken) {
+        steps_saved += a.steps - st0;
+        dead = true;
+      } else if (!dead && bound_proof(st0)) {
+        dead = true;
+      }
     }
     const unsigned long long below = (1ull << lane) - 1ull;
     for (int st = st0; !dead && st < a.steps; ++st) {

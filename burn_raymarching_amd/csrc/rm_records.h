@@ -21,7 +21,7 @@
 //   5. the tail (RecTail), of one size for every scene: the march's escape thresholds (write_bound); camera
 //      mode's origin rows (write_origins), per view the first march step's D at the eye and a lower bound on the
 //      eye's distance to the nearest sphere centre (the march's clamp-free proof, rho_lb in rm_ray_kernel); the
-//      geometry of the call's escape lattice (Lat; write_bound, bound_proof in rm_ray_kernel): {x, y, z of cell
+//      geometry of the call's escape lattice (Lat; write_bound, rm_tile_proof_kernel, bound_proof): {x, y, z of cell
 //      centre 0, h, half-side, 1 / h, slack, 0} -- from the scene's bounding sphere, which only the record
 //      kernel knows, so it lives here and not in KArgs.
 typedef float f4v __attribute__((ext_vector_type(4)));
@@ -235,13 +235,15 @@ __device__ __forceinline__ void scene_bound(const KArgs& a, float* scratch, int 
 // slower with the proof. A call without the proof (KArgs::proof, march_policy) launches the kernel
 // instance without it, and its record kernel skips the pass: R_soft = R + ln(M)/k, the ball's bound.
 constexpr int kProofMinSpheres = 128;
-// The escape lattice of the camera-mode proof (bound_proof; KArgs::lattice): kLatticeN^3 cells over the cube
+// The escape lattice of the camera-mode proof (rm_tile_proof_kernel, bound_proof; KArgs::lattice): kLatticeN^3 cells over the cube
 // of half-side R' + kLatticeMargin about c_0. Sized by tools/escape_proof_sim.py on the bench scene after
 // 35 optimizer steps (profiles/r19_escape_lattice_sim.txt): 64 cells save 26.7 % of the march's packed
 // column blocks where the soft ball alone saves 2.9 %; 96 / 128 add 2 / 4 points for 3.4 / 8 times the fill
 // and a table of 3.5 / 8 MB against the 4 MB L2; the margin hardly matters (0.1 / 0.25 / 0.5: 27.0 / 26.7 / 25.7 %).
 constexpr int kLatticeN = 64;
 constexpr float kLatticeMargin = 0.25f;
+// the bound step at or below which a proof gives its wave up (bound_proof in rm_ray_kernel, rm_tile_proof_kernel)
+constexpr float kProofMinStep = 0.02f;
 __device__ __forceinline__ float soft_radius(const KArgs& a, float* scratch, int tid, const float c0[3], float R) {
   const int lane = tid & 63, wave = tid >> 6, nt = (int)blockDim.x, nw = nt >> 6;
   const float kappa = a.k * kLog2e;
@@ -284,10 +286,11 @@ __device__ void write_bound(const KArgs& a, float* hdr, RecTail* tail) {
     hdr[Hdr::kCz] = c[2];
     hdr[Hdr::kR] = R;
     if (a.lattice != nullptr) {
-      // The escape lattice of this call (kLatticeN; rm_lattice_kernel fills it, bound_proof reads it): the
+      // The escape lattice of this call (kLatticeN; rm_lattice_kernel fills it, rm_tile_proof_kernel or bound_proof reads it): the
       // cube of half-side R' + kLatticeMargin about c_0 in kLatticeN^3 cells of side h, cell i's centre at
       // -half + (i + 0.5) h per axis. The division is done here, once: the ray kernel multiplies by 1 / h.
-      // slack: see bound_proof.
+      // slack: the per-ray lookup's half-diagonal allowance, see bound_proof; the tile proof takes actual
+      // distances and does not read it.
       const float half = (R + a.lse_slack + 1e-3f) * (1.0f + 1e-6f) + kLatticeMargin;
       const float h = 2.0f * half / (float)kLatticeN;
       for (int k = 0; k < 3; ++k) tail->lat[Lat::kX0 + k] = (c[k] - half) + 0.5f * h;

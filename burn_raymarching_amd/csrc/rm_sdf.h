@@ -173,10 +173,161 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_sdf_kernel(const 
   sdf_body<GRID, FULL, false>(a);
 }
 
-// The escape lattice of a call (KArgs::lattice; bound_proof in rm_ray_kernel): the distance-only lattice
+// The escape lattice of a call (KArgs::lattice; rm_tile_proof_kernel below reads it): the distance-only lattice
 // sweep above, bit for bit, at the cell centres write_bound laid out for this call's scene.
 __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_lattice_kernel(const SdfArgs a) {
   sdf_body<true, false, true>(a);
+}
+
+// ---- the tile proof: rm_tile_proof_kernel (KArgs::tile_proof; the escape proof of rm_ray_kernel) ----
+// The lattice's part of the escape proof of a camera call (KArgs::proof == 2), ahead of the per-ray launch:
+// one lane per wave tile of the coming per-ray launch -- rays [64 w, 64 w + 64) of the launch, wave w & 3 of
+// logical block w >> 2, which setup_ray's 16x16 tiling makes one 8x8 pixel quadrant of one view -- marches ONE
+// bound trajectory for the tile's 64 rays and writes taken[w] = 1 when every ray of the tile is proven gone,
+// 0 when it is not known. A wave whose byte is 1 stops where bound_proof would have stopped it; a wave whose
+// byte is 0 runs the soft-ball bound_proof, so the waves taken are a superset of the soft ball's.
+//
+// The cone. The rays of a tile share the eye o, and after the origin step they share t (rays already gone
+// step differently, and need no proof). d_c is the normalised sum of the tile's four corner rays and
+// delta >= |d_r - d_c| for every ray r of the tile: the pixel rectangle is a convex quadrilateral of the image
+// plane, its central projection a convex spherical quadrilateral far inside a hemisphere about d_c, and the
+// distance from d_c is convex along great-circle arcs there, so it is largest at a corner. The corners are the
+// tile's own corner pixels' rays (camera_ray maps pixel x to x / W, not to its centre), in their fp32 bits;
+// the other rays' fp32 directions lie within 2e-7 of the exact quadrilateral, and delta is taken 1e-4
+// relative + 2e-6 up. With p_c(u) = o + d_c u, every ray has |p_r(u) - p_c(u)| <= |u| delta, and D is 1-Lipschitz:
+//   t_r + D(p_r(t_r)) >= u + D(p_r(u)) >= u + L(p_c(u)) - |u| delta        for u <= t_r, any L <= D,
+// so u <- u + L(p_c(u)) - |u| delta stays at or behind every ray's march step for step, as bound_proof's u does
+// for its own ray. The tile is proven at a bound step once wave_escaped's test holds at p_r(u) for every
+// r, in the conservative forms
+//   distance   |p_c - c_0| - |u| delta >= T(steps left) / (1 - 2e-5)        (|p_r - c_0| >= |p_c - c_0| - |u| delta)
+//   receding   (o - c_0) . d_c - |o - c_0| delta + u (1 -+ 2e-6) >= 0       ((p_r - c_0) . d_r = (o - c_0) . d_r + u |d_r|^2)
+// (the sign of the 2e-6 that makes the term smaller); the ray at t_r >= u is then receding and at least as far out.
+// The spare-lane alternative (the per-ray test, 64 lanes per tile) was not taken: one lane per tile is the point.
+//
+// The bound. L = max(|p - c_0| - R_soft, max over the 8 lattice points n around p of G[n] - |p - x_n|), less the
+// margins: D(p) >= D(x_n) - |p - x_n| holds for EVERY lattice point, so the cell's half-diagonal slack and the
+// cell-index rounding argument of a one-cell lookup are not needed, and no inside test either -- the base index
+// is held to [0, N - 2] per axis, and a far lattice point only gives a weak bound. x_n is formed as
+// rm_lattice_kernel forms it, origin + (float)i h in fp32 without contraction: the same bits, the point G[n] was
+// evaluated at. Margins. The pre-pass is latency-bound (one lane per tile: a 10-view call is 640 waves of it, each
+// a chain of up to S dependent bound steps), so a bound step is kept short. The cone's own state -- u, p_c, e,
+// the sums of squares, the tests -- runs in fp64 (contraction off), roundings below 1e-13 at the magnitudes the
+// guard B <= 256 admits. Its square roots are fp32 (v_sqrt_f32 of the fp64 sum rounded to fp32: 6e-8 + 1.2e-7
+// relative; no fp64 square root or division in the loop) and each is taken 1e-6 relative to the safe side: up
+// (sqrt_up; + 1e-15 for an argument fp32 flushes to 0) for |o - c_0| and delta, down (sqrt_down) for |p_c - c_0|,
+// which enters the bound step and the distance test from below. The lattice term is fp32 throughout: p rounded
+// to fp32 (1.5e-5 per axis at B), q = p - x_n (x_n exact: the lattice kernel's bits), the three squares summed,
+// the square root, g - |q| (1 + 2e-6): the relative 2e-6 covers the sum, the root and the last product (4e-7),
+// another 1e-4 absolute the rounding of p and of the difference g - |q| (below 6e-5 at B). The cell index is fp32
+// too and carries no margin: every lattice point gives a valid bound. What remains is what bound_proof
+// charges: R_soft's 1e-3 for the fp32 march of the real rays and 1e-3 per bound step, here on both terms
+// (2e-3), and 1e-3 on the lattice term for rm_lattice_kernel's fp32 (its direct-form distances, one rounding of
+// e at magnitude <= B, 3e-5; square root, sum and logarithm 1e-6 relative): 3.1e-3 in all on the lattice term.
+// The give-up rule is bound_proof's: a net bound step of kProofMinStep or less ends the tile's proof with 0.
+// Tiles that get 0 unseen: a tile whose 64 lanes are not all rays of the launch (none under tiling 2: a view is
+// whole 256-ray blocks), the magnitude guard. The host launches this kernel only for tiled launches large enough
+// to pay for it (tile_proof_policy, rm_launch.h): in rows order (tiling != 2) a wave is no pixel rectangle, and
+// those launches and the small ones read the lattice per ray inside bound_proof instead. A wave whose byte is 0
+// pays for the soft ball twice -- this trajectory's L held the soft-ball term already -- which keeps the taken
+// set a superset of the soft ball's by construction and costs such a wave one more soft-ball bound march.
+__device__ __forceinline__ double sqrt_up(double x) { return (double)fsqrt((float)x) * (1.0 + 1e-6) + 1e-15; }
+__device__ __forceinline__ double sqrt_down(double x) { return (double)fsqrt((float)x) * (1.0 - 1e-6); }
+__device__ __forceinline__ bool tile_proven(const KArgs& a, long long w) {
+#pragma clang fp contract(off)
+  if (a.tiling != 2 || !(a.gone_d > 0.0f) || a.lattice == nullptr || 64 * w + 64 > a.n_rays) return false;
+  const long long npix = (long long)a.width * a.height, ri = a.ray_begin + 64 * w;
+  const int v = (int)(ri / npix);
+  const long long pix = ri - (long long)v * npix, tl = pix >> 8;
+  if ((ri + 63) / npix != v) return false;
+  const int qd = (int)(pix & 255) >> 6, tiles_x = a.width >> 4;
+  const int ty = (int)(tl / tiles_x), tx = (int)(tl - (long long)ty * tiles_x);
+  const int x0 = (tx << 4) + ((qd & 1) << 3), y0 = (ty << 4) + ((qd >> 1) << 3);  // setup_ray's lane 0
+  const CamBasis& cam = a.cams_dev != nullptr ? a.cams_dev[v] : a.cams[v];
+
+  const Lds L = bind_records(a.rec_buf, a.Mpad);
+  const cf1_ptr hdr = rec_header(L, a.Mpad);
+  const cf1_ptr esc_tab = (cf1_ptr)RecLayout::at<const char>(a.rec_buf, RecLayout(a.Mpad).esc());
+  const cf1_ptr lg = (cf1_ptr)RecLayout::at<const char>(a.rec_buf, RecLayout(a.Mpad).lattice());
+  const float c0x = hdr[Hdr::kCx], c0y = hdr[Hdr::kCy], c0z = hdr[Hdr::kCz];
+
+  float o[3], dk[4][3];
+  for (int k = 0; k < 4; ++k) camera_ray(cam, x0 + 7 * (k & 1), y0 + 7 * (k >> 1), a.width, a.height, o, dk[k]);
+  // bound_proof's magnitude guard, in its fp32 form
+  if (!(fabsf(o[0]) + fabsf(o[1]) + fabsf(o[2]) + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= 256.0f))
+    return false;
+  double dc[3];
+  for (int k = 0; k < 3; ++k) dc[k] = ((double)dk[0][k] + (double)dk[1][k]) + ((double)dk[2][k] + (double)dk[3][k]);
+  // d_c need not be a unit vector to the last bit: delta is taken against the d_c used, and nothing else asks
+  const double il = (double)frsq((float)(dc[0] * dc[0] + dc[1] * dc[1] + dc[2] * dc[2]));
+  for (int k = 0; k < 3; ++k) dc[k] *= il;
+  double delta = 0.0;
+  for (int k = 0; k < 4; ++k) {
+    const double ex = (double)dk[k][0] - dc[0], ey = (double)dk[k][1] - dc[1], ez = (double)dk[k][2] - dc[2];
+    delta = fmax(delta, sqrt_up(ex * ex + ey * ey + ez * ez));
+  }
+  delta = delta * (1.0 + 1e-4) + 2e-6;
+
+  const double c0[3] = {(double)c0x, (double)c0y, (double)c0z};
+  const double oc[3] = {(double)o[0] - c0[0], (double)o[1] - c0[1], (double)o[2] - c0[2]};
+  const double rec0 = (oc[0] * dc[0] + oc[1] * dc[1] + oc[2] * dc[2]) -
+                      sqrt_up(oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2]) * delta;
+  const double rs = (double)((hdr[Hdr::kRsoft] + 1e-3f) * (1.0f + 1e-6f) + 1e-3f);  // bound_proof's rs
+  const float h = lg[Lat::kH], x0f[3] = {lg[Lat::kX0], lg[Lat::kY0], lg[Lat::kZ0]};
+  const float half = lg[Lat::kHalf], inv_h = lg[Lat::kInvH];
+
+  // the state the per-ray kernel's waves bring to bound_proof: after the shared origin step where it is taken
+  double u = 0.0;
+  int st0 = 0;
+  if (a.origin != nullptr && a.steps > 0) {
+    const float D0 = a.origin[RecTail::kD0 + v];
+    if ((__float_as_uint(D0) & 0x7fffffffu) <= 0x7f800000u) {
+      u = (double)fminf(D0, kTMax);
+      st0 = 1;
+    }
+  }
+  for (int n = st0; n < a.steps; ++n) {
+    const double p[3] = {(double)o[0] + dc[0] * u, (double)o[1] + dc[1] * u, (double)o[2] + dc[2] * u};
+    const double e[3] = {p[0] - c0[0], p[1] - c0[1], p[2] - c0[2]};
+    const double dist = sqrt_down(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);  // enters both uses from below
+    const double ud = fabs(u) * delta;
+    const double Tn = (double)esc_tab[min(a.steps - n, kEscTab - 1)];
+    if (rec0 + u * (u >= 0.0 ? 1.0 - 2e-6 : 1.0 + 2e-6) >= 0.0 && dist - ud >= Tn * 1.0000200005) return true;  // >= Tn / (1 - 2e-5)
+    double Lb = dist - rs;
+    // the lattice term, fp32: per axis the base index (>= 0: the conversion truncates as floor would) and the
+    // squared offsets of p from the two lattice planes beside it; then the 8 points, one base address
+    int i0[3];
+    float q2[3][2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float f = fminf(fmaxf(((float)e[k] + half) * inv_h - 0.5f, 0.0f), (float)(kLatticeN - 2));
+      i0[k] = (int)f;
+      const float pk = (float)p[k];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const float q = pk - (x0f[k] + (float)(i0[k] + j) * h);
+        q2[k][j] = q * q;
+      }
+    }
+    const float* g0 = a.lattice + (i0[2] * kLatticeN + i0[1]) * kLatticeN + i0[0];
+    float best = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+      const int jx = c & 1, jy = (c >> 1) & 1, jz = c >> 2;
+      const float dn = fsqrt(q2[0][jx] + q2[1][jy] + q2[2][jz]);
+      best = fmaxf(best, fmaf(dn, -(1.0f + 2e-6f), g0[(jz * kLatticeN + jy) * kLatticeN + jx]));
+    }
+    Lb = fmax(Lb, (double)best - 3.1e-3);
+    const double step = Lb - ud;
+    if (!(step > (double)kProofMinStep)) return false;
+    u += step;
+  }
+  return false;
+}
+
+__global__ __launch_bounds__(kBlock) void rm_tile_proof_kernel(const KArgs a, unsigned char* __restrict__ taken,
+                                                               long long n_tiles) {
+  const long long w = (long long)blockIdx.x * kBlock + threadIdx.x;
+  if (w < n_tiles) taken[w] = tile_proven(a, w) ? 1 : 0;
 }
 
 // ---- the field's backward: rm_sdf_grad_kernel (rm_sdf_query_backward) -------------------------

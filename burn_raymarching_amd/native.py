@@ -128,6 +128,7 @@ SIGNATURES = {
                                               ctypes.POINTER(RmMarch), _P]),
     "rm_debug_order_counts": (ctypes.c_int, [_P, ctypes.POINTER(_I32), _I32, ctypes.POINTER(_I32),
                                              ctypes.POINTER(_I32)]),
+    "rm_debug_tile_proof": (ctypes.c_int, [_P, _P, _I64, ctypes.POINTER(_I64)]),
     "rm_debug_stall": (ctypes.c_int, [_P, _I32]),
     "rm_debug_stall_release": (ctypes.c_int, [_P]),
     "rm_timing_enable": (ctypes.c_int, [_P, _I32]),
@@ -239,6 +240,15 @@ class Context:
                    "rm_debug_order_counts")
         c = cls.value
         return [list(buf[i * c:(i + 1) * c]) for i in range(3)], nxt.value
+
+    def tile_proof(self, capacity: int = 1 << 20) -> bytes:
+        """rm_debug_tile_proof: the per-wave bytes of the context's last per-ray launch (1: the pre-pass
+        proved the wave gone); empty when that launch took no tile proof. A call split over several
+        launches shows its last launch's waves only."""
+        buf = (ctypes.c_uint8 * capacity)()
+        n = _I64()
+        self.check(self._lib.rm_debug_tile_proof(self.handle, buf, capacity, ctypes.byref(n)), "rm_debug_tile_proof")
+        return bytes(buf[:n.value])
 
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:

@@ -465,6 +465,14 @@ int rm_debug_intermediates(rm_context* ctx, const float* ray_org, const float* r
  * uncleared (the state a failed launch in the rotation leaves), for the recovery test. */
 int rm_debug_order_counts(rm_context* ctx, int32_t* counts, int32_t capacity, int32_t* classes, int32_t* next_set);
 
+/* The tile proof of the escape lattice (tests): after synchronising the stream, copies the bytes the last
+ * per-ray launch of a camera call with the lattice read -- one per wave (64 rays; wave w & 3 of ray block
+ * w >> 2, an 8x8 pixel quadrant of a 16x16 tile), 1 where the pre-pass proved every ray of the wave gone, 0
+ * where it did not -- into host[0 .. min(capacity, waves)); *n_waves = the bytes copied. Only the context's
+ * LAST per-ray launch is seen: 0 bytes when that launch took no tile proof (no lattice, row order, a launch
+ * below the tile proof's size), and of a call split over several launches the last launch's waves alone. */
+int rm_debug_tile_proof(rm_context* ctx, uint8_t* host, int64_t capacity, int64_t* n_waves);
+
 /* Stream stall (tests of a caller's watchdog, e.g. rmh_collective.wait): enqueues on the context's
  * stream one wave that spins until rm_debug_stall_release(ctx) or until max_ms (1 .. 600000) have
  * passed, whichever comes first -- it always ends by itself. rm_destroy releases a pending one. */

@@ -27,6 +27,11 @@ Bound families:
             half-diagonal from its centre; the cell is floor((p - c_0 + half) / h) per axis, and outside the cube the
             bound is the soft ball alone. One table read per bound step whatever N: K = 1 in the cost model, the
             lattice build (N^3 M evaluations per call) not counted
+  ngridN[:m] the same lattice read at the 8 points around p, each with its actual distance: max_n G[n] - |p - x_n|
+            (1 + 1e-6) - 2e-3, and the soft ball. No half-diagonal slack, no inside test. K = 8
+  cone:FAM  FAM's bound marched once per tile instead of once per ray (rm_tile_proof_kernel): the centre direction
+            of the tile's corner rays, every step less |u| delta, the conservative distance and receding tests
+            (prove_cone). Cost: a 64th of a wave's bound step per tile step
 
 softball, radial and radtab print the same figures on the bench scenes: every proof the radial bound finds
 comes from rho past the outermost centre, where it is exactly rho - R_soft. That is the finding the kernel
@@ -106,9 +111,10 @@ def bound_fn(family, c, r, c0, rp, k):
             cell = np.minimum((rho / h).astype(np.int64), 254)
             return np.where(rho / h < 255, np.maximum(tab[cell], rho - rs), rho - rs)
         return L, 1
-    if family.startswith("grid"):
+    if family.startswith("grid") or family.startswith("ngrid"):
         name, _, mg = family.partition(":")
-        N, margin = int(name[4:]), float(mg) if mg else 0.25
+        neighbours = name.startswith("n")
+        N, margin = int(name[5 if neighbours else 4:]), float(mg) if mg else 0.25
         Ls = bound_fn("softball", c, r, c0, rp, k)[0]
         half = F(rp + margin)
         h = F(2) * half / F(N)
@@ -121,6 +127,17 @@ def bound_fn(family, c, r, c0, rp, k):
             x = -k * (np.sqrt(np.maximum((e * e).sum(-1), F(1e-6))) - r)
             m = x.max(-1)
             G[iz] = -(m + np.log(np.exp(x - m[..., None]).sum(-1, dtype=F))) / k
+        if neighbours:
+            def Ln(p):  # the 8 lattice points around p, each with its actual distance; no inside test (base index held)
+                e = (p - c0).astype(np.float64)
+                i0 = np.floor(np.clip((e + half) * inv_h - 0.5, 0, N - 2)).astype(np.int64)
+                best = Ls(p).astype(np.float64)
+                for cnr in range(8):
+                    i = i0 + np.array([cnr & 1, (cnr >> 1) & 1, cnr >> 2])
+                    dn = np.sqrt(((e - ax[i]) ** 2).sum(-1))
+                    best = np.maximum(best, G[i[..., 2], i[..., 1], i[..., 0]] - dn * (1 + 1e-6) - 2e-3)
+                return best.astype(F)
+            return Ln, 8
         G -= h * F(math.sqrt(3) / 2 * (1 + 1e-5)) + F(1e-3)
 
         def L(p):
@@ -161,6 +178,41 @@ def prove(L, o, d, t, gone, st, S, c0, T, min_step=0.0):
         idx = np.flatnonzero(alive)
         alive[idx[stuck]] = False
     return proven.all(1), steps_run
+
+
+def prove_cone(L, o, d, t, gone, st, S, c0, T, min_step=0.0):
+    """One bound march per tile [n, 64] (rm_tile_proof_kernel's conservative cone): d_c the normalised sum of the
+    tile's corner rays, delta >= |d_r - d_c|, u <- u + L(p_c(u)) - 1e-3 - |u| delta from the smallest t of the lanes
+    not gone; proven once (o - c_0) . d_c - |o - c_0| delta + u (1 - 2e-6) >= 0 and
+    |p_c - c_0| - |u| delta >= T(steps left) / (1 - 2e-5)."""
+    d4 = d[:, [0, 7, 56, 63]].astype(np.float64)
+    dc = d4.sum(1)
+    dc /= np.linalg.norm(dc, axis=-1, keepdims=True)
+    delta = np.linalg.norm(d4 - dc[:, None], axis=-1).max(1) * (1 + 1e-4) + 2e-6
+    eye = o[:, 0].astype(np.float64)
+    oc = eye - c0
+    rec0 = (oc * dc).sum(-1) - np.linalg.norm(oc, axis=-1) * delta
+    alive = ~gone.all(1)
+    u = np.where(gone, np.inf, t).min(1).astype(np.float64)
+    u[~alive] = 0.0
+    ok = ~alive
+    steps_run = np.zeros(len(u))
+    for n in range(st, S):
+        p = eye + dc * u[:, None]
+        dist = np.linalg.norm(p - c0, axis=-1)
+        ud = np.abs(u) * delta
+        prov = alive & (rec0 + u * (1 - 2e-6) >= 0) & (dist - ud >= T[S - n] / (1 - 2e-5))
+        ok |= prov
+        alive &= ~prov
+        if not alive.any():
+            break
+        step = L(p[alive].astype(F)).astype(np.float64) - 1e-3 - ud[alive]
+        steps_run[alive] += 1
+        idx = np.flatnonzero(alive)
+        stuck = step <= min_step
+        u[idx] += np.where(stuck, 0.0, step)
+        alive[idx[stuck]] = False
+    return ok, steps_run / 64.0  # one lane per tile: a 64th of a wave's bound step
 
 
 def main():
@@ -250,7 +302,8 @@ def main():
     print("  family    waves proven@1  (retries)  wave-steps saved@1 (retries)  blocks saved@1 (retries)"
           "  cost@1 (retries)  net wave-steps@1 (retries)")
     for family in args.families.split(","):
-        L, K = bound_fn(family, c, r, c0, rp, k)
+        is_cone = family.startswith("cone:")
+        L, K = bound_fn(family[5:] if is_cone else family, c, r, c0, rp, k)
         done = np.zeros(n, bool)
         res = []
         sv_w = sv_b = cost = 0.0
@@ -258,7 +311,7 @@ def main():
             ts, gs, rs = snap.get(st, (None, None, np.zeros(n, bool)))
             w = rs & ~done
             if w.any():
-                ok, steps_run = prove(L, o[w], d[w], ts[w], gs[w], st, S, c0, T, args.min_step)
+                ok, steps_run = (prove_cone if is_cone else prove)(L, o[w], d[w], ts[w], gs[w], st, S, c0, T, args.min_step)
                 idx = np.flatnonzero(w)[ok]
                 done[idx] = True
                 sv_w += ran[st:, idx].sum()
