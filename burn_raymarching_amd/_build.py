@@ -44,7 +44,7 @@ def _stale(target: str, sources) -> bool:
 # The kernel library's sources; their hash is compiled into rm_version() ("src <hash>"), so that a
 # shipped .so names the source it came from (tests/test_abi.py compares it with the tree).
 KERNEL_SOURCES = [os.path.join(CSRC, "rm_kernels.hip"), os.path.join(CSRC, "rm_device.h"),
-                  os.path.join(CSRC, "rm_records.h"),
+                  os.path.join(CSRC, "rm_proof.h"), os.path.join(CSRC, "rm_records.h"),
                   os.path.join(CSRC, "rm_reduce.h"), os.path.join(CSRC, "rm_small.h"),
                   os.path.join(CSRC, "rm_raygrad.h"), os.path.join(CSRC, "rm_view.h"),
                   os.path.join(CSRC, "rm_sdf.h"),

@@ -321,9 +321,7 @@ int rm_reserve(rm_context* ctx, int64_t max_rays, int32_t max_spheres) {
   {  // the sphere records: all the scratch rm_view takes
     if ((rc = ctx->rec.ensure(ctx, RecLayout(pad_spheres(max_spheres)).bytes(), "record buffer")) != RM_OK) return rc;
   }
-  if (rays >= kLatticeMinRays && pad_spheres(max_spheres) >= kProofMinSpheres &&
-      ((rc = ctx->lattice.ensure(ctx, sizeof(float) * kLatticeCells, "escape lattice")) != RM_OK ||
-       (rc = ctx->tile_proof.ensure(ctx, (size_t)kMaxBlocksPerLaunch * kWaves, "tile proof")) != RM_OK))
+  if (rays >= kLatticeMinRays && pad_spheres(max_spheres) >= kProofMinSpheres && (rc = ensure_proof_buffers(ctx)) != RM_OK)
     return rc;
   return ctx->ws.ensure(ctx, ws_need(rays, max_spheres), "workspace");
 }

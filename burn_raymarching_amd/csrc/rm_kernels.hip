@@ -104,7 +104,7 @@ struct KArgs {
                               // backward sweeps run for (non-zero seeds)
   float gone_d;               // > 0: rays that provably escape past this distance are `gone` (see the march)
   int early_exit;             // waves whose rays are all gone stop marching
-  int proof;                  // the escape proof before the march (rm_ray_kernel<.., PROOF>; march_policy): 1 the
+  int proof;                  // the escape proof before the march (rm_ray_kernel<.., PROOF>; proof_tier): 1 the
                               // soft ball alone, 2 with the call's lattice (the tile proof before the launch, or per ray in bound_proof)
   int split;                  // split march (RM_MARCH_SPLIT): kSplitRays rays per block, a quarter of the spheres per wave
   int mfma;                   // march sums on the matrix cores (lse_mfma) instead of lse_weighted
@@ -268,6 +268,7 @@ __device__ __forceinline__ uint4 mfma_a_frag(const KArgs& a, int e) {
 __device__ __forceinline__ int mfma_w_sphere(int e) { return 16 * (e >> 5) + (e & 15); }
 __device__ __forceinline__ bool mfma_w_fixed(int e) { return (e & 16) != 0; }
 
+#include "rm_proof.h"
 #include "rm_records.h"
 
 // ---- packed helpers --------------------------------------------------------------------------

@@ -398,11 +398,57 @@ int prepare_records(rm_context* ctx, KArgs& a, bool origin) {
   return RM_OK;
 }
 
+// ---- the escape proof ------------------------------------------------------------------------
+// The host's side of the escape proof (rm_proof.h; bound_proof in rm_ray.h, rm_tile_proof_kernel in rm_sdf.h):
+// which tier a call runs (proof_tier, once per call), its two context buffers (ensure_proof_buffers), the
+// call's lattice (prepare_records_and_lattice) and the tile proof of a launch (tile_proof_policy, tile_proof).
+// On the call's stream, in this order: records, origin step, lattice fill; then per launch the tile proof and
+// the per-ray launch that reads it.
+constexpr size_t kLatticeCells = (size_t)kLatticeN * kLatticeN * kLatticeN;
+// The escape lattice costs a call one rm_lattice_kernel launch (kLatticeN^3 M evaluations, about 24 us at
+// 256 spheres) whatever its size, and saves in proportion to its rays. Measured on the bench scene, 512x512
+// views of 256 spheres, lattice against soft ball alone (profiles/r19_escape_lattice_ab.txt): 80 views
+// +12.7 %, 10 views +10 %, 4 views +4.5 %, 2 views -1 % (inside the noise), 1 view -5 %, a 256x256 view
+// -11 %. Camera calls below kLatticeMinRays rays (4 views of 512x512) keep the soft ball alone.
+constexpr long long kLatticeMinRays = 1048576;
+// The tile proof needs the 16x16 tiling -- in rows order a wave's 64 rays are no pixel rectangle and have no
+// narrow cone -- and a launch large enough to pay for it: one lane per tile, each a chain of up to `steps`
+// dependent bound steps of about 0.4 us, it takes 26 us at 10 views of 512x512 and 32 steps however few tiles
+// there are, and 42 us at 80 views. Measured against the per-ray lookup (profiles/r20_tile_proof_ab.txt): 80
+// views +3.8 %, 10 views a tie at 32 steps and -0.6 to -0.9 % at 64 steps. Launches below kTileProofMinRays
+// rays (20 views of 512x512) keep the per-ray lookup.
+constexpr long long kTileProofMinRays = 5242880;
+
+// What a call runs of the proof: KArgs::proof, and whether env RM_PROOF_LATTICE=1 asked for the lattice.
+struct ProofTier {
+  enum { kNone = 0, kBall = 1, kLattice = 2 };
+  int tier;
+  bool forced;  // the lattice at any call size, and the tile proof at any launch size
+};
+// The proof at all: the unsplit training kernels with the exit on (hence no per-ray t and no debug output),
+// from kProofMinSpheres spheres on. With the call's escape lattice: camera calls of at least kLatticeMinRays
+// rays; env RM_PROOF_LATTICE=0 never, =1 at any size (read once per call, as RM_SPLIT). Other calls keep the
+// soft ball alone.
+ProofTier proof_tier(bool early_exit, bool split, int mode, int Mpad, bool cam, long long rays) {
+  if (!early_exit || split || mode == kRender || Mpad < kProofMinSpheres) return {ProofTier::kNone, false};
+  if (!cam) return {ProofTier::kBall, false};
+  const char* e = std::getenv("RM_PROOF_LATTICE");
+  const bool never = e && e[0] == '0', forced = e && e[0] == '1';
+  if (never || !(rays >= kLatticeMinRays || forced)) return {ProofTier::kBall, false};
+  return {ProofTier::kLattice, forced};
+}
+
+// The lattice (kLatticeN^3 floats) and the tile-proof bytes (one per wave of the largest launch) of a context.
+int ensure_proof_buffers(rm_context* ctx) {
+  int rc;
+  if ((rc = ctx->lattice.ensure(ctx, sizeof(float) * kLatticeCells, "escape lattice")) != RM_OK) return rc;
+  return ctx->tile_proof.ensure(ctx, (size_t)kMaxBlocksPerLaunch * kWaves, "tile proof");
+}
+
 // The call's escape lattice (KArgs::lattice; rm_tile_proof_kernel or bound_proof reads it): the soft-min at the
 // kLatticeN^3 cell centres the record kernel laid out, by the distance-only lattice sweep of
 // rm_sdf_grid. Once per call, after the record kernels and before the per-ray launches, on the call's
 // stream: the scene changes with every optimizer step, so nothing of it is kept across calls.
-constexpr size_t kLatticeCells = (size_t)kLatticeN * kLatticeN * kLatticeN;
 int fill_lattice(rm_context* ctx, const KArgs& a) {
   SdfArgs s;
   std::memset(&s, 0, sizeof s);
@@ -420,28 +466,36 @@ int fill_lattice(rm_context* ctx, const KArgs& a) {
   return RM_OK;
 }
 
-// Where a launch of a call with the lattice reads it: in the tile proof before the launch (true) or per ray
-// inside bound_proof (false; rm_ray.h). The tile proof needs the 16x16 tiling -- in rows order a wave's 64
-// rays are no pixel rectangle and have no narrow cone -- and a launch large enough to pay for it: one lane per
-// tile, each a chain of up to `steps` dependent bound steps of about 0.4 us, it takes 26 us at 10 views of
-// 512x512 and 32 steps however few tiles there are, and 42 us at 80 views. Measured against the per-ray lookup
-// (profiles/r20_tile_proof_ab.txt): 80 views +3.8 %, 10 views a tie at 32 steps and -0.6 to -0.9 % at 64
-// steps. Launches below kTileProofMinRays rays (20 views of 512x512) keep the per-ray lookup; env
-// RM_PROOF_LATTICE=1 takes the tile proof at any size. Either way the same waves' results: what a proof
-// tries changes none.
-constexpr long long kTileProofMinRays = 5242880;
-bool tile_proof_policy(const KArgs& a, long long nr) {
-  return a.lattice != nullptr && a.tiling == 2 && (nr >= kTileProofMinRays || env_is("RM_PROOF_LATTICE", '1'));
+// The records of a call (prepare_records) and, at the lattice tier, its lattice. KArgs::lattice is bound before
+// the record kernel, which lays the lattice out only for a call that has one (write_bound); the fill follows.
+int prepare_records_and_lattice(rm_context* ctx, KArgs& a, bool origin, const ProofTier& proof) {
+  int rc;
+  if (proof.tier == ProofTier::kLattice) {
+    if ((rc = ensure_proof_buffers(ctx)) != RM_OK) return rc;
+    a.lattice = ctx->lattice.as<float>();
+  }
+  if ((rc = prepare_records(ctx, a, origin)) != RM_OK) return rc;
+  return a.lattice != nullptr ? fill_lattice(ctx, a) : RM_OK;
 }
 
-// The tile proof of one per-ray launch of a call with the lattice (KArgs::tile_proof; rm_tile_proof_kernel):
-// a byte per wave of the launch's nb blocks, written on the call's stream after the lattice and the origin
-// kernel and before the per-ray launch, which reads it. Nothing of it is kept: every launch writes all of its
-// bytes, inside a captured graph as outside.
-int tile_proof(rm_context* ctx, KArgs& a, long long nb) {
-  int rc;
-  if ((rc = ctx->tile_proof.ensure(ctx, (size_t)kMaxBlocksPerLaunch * kWaves, "tile proof")) != RM_OK) return rc;
-  unsigned char* taken = ctx->tile_proof.as<unsigned char>();
+// Where a launch of a call with the lattice reads it: in the tile proof before the launch (true) or per ray
+// inside bound_proof (false; rm_ray.h): tiled launches of at least kTileProofMinRays rays (the measurements
+// above), or of any size when the call's lattice was forced. Either way the same waves' results: what a proof
+// tries changes none.
+bool tile_proof_policy(const KArgs& a, const ProofTier& proof, long long nr) {
+  return proof.tier == ProofTier::kLattice && a.tiling == 2 && (nr >= kTileProofMinRays || proof.forced);
+}
+
+// The tile proof of one per-ray launch of nb blocks and nr rays (KArgs::tile_proof; rm_tile_proof_kernel), where
+// the policy takes it: a byte per wave of the launch, written on the call's stream after the lattice and the
+// origin kernel and before the per-ray launch, which reads it. Nothing of it is kept: every launch writes all
+// of its bytes, inside a captured graph as outside, and a launch without the tile proof leaves none
+// (rm_debug_tile_proof).
+int tile_proof(rm_context* ctx, KArgs& a, const ProofTier& proof, long long nb, long long nr) {
+  a.tile_proof = nullptr;
+  ctx->tile_proof_n = 0;
+  if (nb <= 0 || !tile_proof_policy(a, proof, nr)) return RM_OK;
+  unsigned char* taken = ctx->tile_proof.as<unsigned char>();  // ensure_proof_buffers, with the call's lattice
   const long long n_tiles = nb * kWaves;
   hipLaunchKernelGGL(rm_tile_proof_kernel, dim3((unsigned)((n_tiles + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
                      a, taken, n_tiles);
@@ -697,16 +751,10 @@ int check_call(rm_context* ctx, const Call& c, long long n) {
   return RM_OK;
 }
 
-// The escape lattice costs a call one rm_lattice_kernel launch (kLatticeN^3 M evaluations, about 24 us at
-// 256 spheres) whatever its size, and saves in proportion to its rays. Measured on the bench scene, 512x512
-// views of 256 spheres, lattice against soft ball alone (profiles/r19_escape_lattice_ab.txt): 80 views
-// +12.7 %, 10 views +10 %, 4 views +4.5 %, 2 views -1 % (inside the noise), 1 view -5 %, a 256x256 view
-// -11 %. Camera calls below kLatticeMinRays rays (4 views of 512x512) keep the soft ball alone.
-constexpr long long kLatticeMinRays = 1048576;
-
-// How the call marches, into KArgs: the split march, the escape pre-pass, the early exit and the
-// flags that select march paths. Returns whether the call takes the split march.
-bool march_policy(const Call& c, long long n, KArgs& a) {
+// How the call marches, into KArgs: the split march, the escape pre-pass, the early exit, the escape proof's
+// tier (also handed back: `proof`) and the flags that select march paths. Returns whether the call takes the
+// split march.
+bool march_policy(const Call& c, long long n, KArgs& a, ProofTier& proof) {
   const int M = a.M;
   // Escape skipping needs the mask to be exactly 0 at the certified distance: sigmoid(-msharp D)
   // once msharp log2(e) D > 128 overflows exp2 (use 160), exp(-10 D^2) in kRender long before 50.
@@ -737,14 +785,8 @@ bool march_policy(const Call& c, long long n, KArgs& a) {
     else if (a.msharp > 0.0f) a.gone_d = std::max(6.0f, 130.0f / (a.msharp * 1.44269504f));
   }
   a.early_exit = a.gone_d > 0.0f && (c.march->flags & RM_MARCH_NO_EARLY_EXIT) == 0 && !c.t_out ? 1 : 0;
-  // the escape proof (rm_ray.h, bound_proof): the unsplit training kernels with the exit on (hence no
-  // per-ray t and no debug output), from kProofMinSpheres spheres on
-  a.proof = a.early_exit && !split && c.mode != kRender && a.Mpad >= kProofMinSpheres ? 1 : 0;
-  // with the call's escape lattice (proof = 2; run() fills it): camera calls of at least kLatticeMinRays
-  // rays; env RM_PROOF_LATTICE=0 never, =1 at any size (read per call, as RM_SPLIT). Other calls keep the
-  // soft ball alone.
-  if (a.proof && c.cam && !env_is("RM_PROOF_LATTICE", '0') && (n >= kLatticeMinRays || env_is("RM_PROOF_LATTICE", '1')))
-    a.proof = 2;
+  proof = proof_tier(a.early_exit != 0, split, c.mode, a.Mpad, c.cam, n);
+  a.proof = proof.tier;
   a.mfma = (c.march->flags & RM_MARCH_VALU_ONLY) == 0;
   a.shift_max = (c.march->flags & RM_MARCH_FORCE_MAX_SHIFT) != 0;
   if (c.mode == kRender) {  // renderer.rs:27-32, normalised in f32 on the host like the reference
@@ -966,16 +1008,12 @@ int run(rm_context* ctx, const Call& c) {
   a.inv_count = c.inv_count;
   a.sdev = ctx->sdev;
   a.dbg = c.dbg;
-  const bool split = march_policy(c, n, a);
+  ProofTier proof;
+  const bool split = march_policy(c, n, a, proof);
   if (use_small(c, a.M, n)) return run_small(ctx, c, a, n);
   if (c.fused) return fail(ctx, RM_ERR_INVALID_ARG, "fused iteration outside the small kernel");
   const bool origin = c.cam && (c.march->flags & (RM_MARCH_PER_RAY_ORIGIN | RM_MARCH_FORCE_MAX_SHIFT)) == 0;
-  if (a.proof == 2 && n > 0) {  // set before the record kernel, which lays the lattice out (write_bound)
-    if ((rc = ctx->lattice.ensure(ctx, sizeof(float) * kLatticeCells, "escape lattice")) != RM_OK) return rc;
-    a.lattice = ctx->lattice.as<float>();
-  }
-  if (n > 0 && (rc = prepare_records(ctx, a, origin)) != RM_OK) return rc;
-  if (a.lattice != nullptr && (rc = fill_lattice(ctx, a)) != RM_OK) return rc;
+  if (n > 0 && (rc = prepare_records_and_lattice(ctx, a, origin, proof)) != RM_OK) return rc;
 
   const int rpb = split ? kSplitRays : kBlock;  // rays per block
   if (has_bwd && (rc = ctx->ws.ensure(ctx, ws_need(std::max<long long>(n, 1), a.M, rpb), "workspace")) != RM_OK)
@@ -1009,9 +1047,7 @@ int run(rm_context* ctx, const Call& c) {
       RM_HIP(ctx, hipGetLastError());
       a.esc_flags = flags;
     }
-    a.tile_proof = nullptr;
-    ctx->tile_proof_n = 0;  // rm_debug_tile_proof: a launch without the tile proof leaves no bytes
-    if (l.nb > 0 && tile_proof_policy(a, l.nr) && (rc = tile_proof(ctx, a, l.nb)) != RM_OK) return rc;
+    if ((rc = tile_proof(ctx, a, proof, l.nb, l.nr)) != RM_OK) return rc;
     if (l.nb > 0) {
 #ifdef RM_BLOCK_TRACE
       if ((rc = bind_block_trace(ctx, a, l.nb * kWaves)) != RM_OK) return rc;

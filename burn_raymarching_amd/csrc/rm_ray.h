@@ -470,7 +470,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   bool dead = false;       // wave-uniform: every ray of the wave has escaped (see below)
   int steps_saved = 0;     // wave-uniform: march steps this wave did not run (work statistics)
   // the scene's bounding sphere (c, R) (scene_bound, in the record header); R' = R + soft-min
-  // slack + 1e-3 (fp32 margin of the march)
+  // slack + the march's allowance (proof_rprime, rm_proof.h)
   const float c0x = hdr[Hdr::kCx], c0y = hdr[Hdr::kCy], c0z = hdr[Hdr::kCz];
   const cf1_ptr esc_tab = (cf1_ptr)RecLayout::at<const char>(a.rec_buf, RecLayout(a.Mpad).esc());
   if (MODE == kBwd && a.t_in != nullptr) {
@@ -481,8 +481,8 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // receding ray, so t keeps increasing); the reconnected point and the mask argument
     // are then >= gone_d too, where sigmoid(-msharp D) (or exp(-10 D^2)) is exactly 0 in
     // fp32: out = 0 and every gradient term is 0, whatever the remaining steps would give.
-    // Margins: 1e-5 relative + 1e-3 cover the fp32 rounding of the march at any |p|.
-    // Each remaining step is >= dist - R' long and keeps the ray receding, so the distance
+    // Margins: kEscapeRel relative + kMarchAbs cover the fp32 rounding of the march at any |p| (the ledger
+    // of rm_proof.h). Each remaining step is >= dist - R' long and keeps the ray receding, so the distance
     // grows step by step (write_bound): with n steps left the ray is gone once
     // (1 - 1e-5) dist >= T(n) -- proven long before the ray gets there.
     // A gone ray (sticky) steps by that bound, dist - R', instead of its soft-min: the proof
@@ -491,14 +491,14 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // the whole wave: 48 % of the march steps at 4096 spheres / 128 steps). A wave whose
     // rays are all gone stops (a.early_exit). The same in every mode that builds the table,
     // exit on or off, so both give the same bits.
-    const float rprime = (hdr[Hdr::kR] + a.lse_slack + 1e-3f) * (1.0f + 1e-6f);  // R' as in write_bound
+    const float rprime = proof_rprime(hdr[Hdr::kR], a.lse_slack);  // R' as in write_bound
     float gone_step = 0.0f;  // dist - R' of a gone ray at the current point
     auto wave_escaped = [&](int st, const float p[3]) {
       if (!(a.gone_d > 0.0f)) return false;
       const float ex = p[0] - c0x, ey = p[1] - c0y, ez = p[2] - c0z;
       const float Tn = esc_tab[min(a.steps - st, kEscTab - 1)];
       const float dist = fsqrt(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
-      gone = gone || (!retired && fmaf(ez, d[2], fmaf(ey, d[1], ex * d[0])) >= 0.0f && dist * (1.0f - 1e-5f) >= Tn);
+      gone = gone || (!retired && fmaf(ez, d[2], fmaf(ey, d[1], ex * d[0])) >= 0.0f && dist * (1.0f - (float)kEscapeRel) >= Tn);
       gone_step = dist - rprime;
       if (a.early_exit && __all(gone || !valid)) {
         steps_saved += a.steps - st;
@@ -531,14 +531,10 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // same outputs (exactly 0). Otherwise nothing changes: a proven ray of a wave that marches on
     // is not marked gone (gone rays leave the wave's votes, which would change other rays' bits).
     // L = |p - c_0| - R_soft (soft_radius): the ball bound without the ln(M)/k that R' charges.
-    // Margins: R_soft carries the march's 1e-3 as R' does; another 1e-3 comes off every bound step
-    // and the distance test takes 2e-5 relative where wave_escaped takes 1e-5. They cover the bound
-    // march's own fp32 rounding: every value in it is at most B = |o|_1 + |c_0|_1 + 3 T(0) in
-    // magnitude (the bound march stops within a step of distance T(0), and a step at most doubles
-    // the distance), the proof is tried only where B <= 256 for every lane of the wave, and its five roundings per step are then
-    // below 256 x 6e-8 each, 1e-4 in all. A wave gives up once a ray's bound step falls to
-    // kProofMinStep (not to 0: a ray creeping along the ball is not proven in the steps left either,
-    // tools/escape_proof_sim.py): what the proof tries changes no result.
+    // Margins: the ball reader of rm_proof.h's ledger -- rs carries the march's allowance as R' does and
+    // another per bound step, the distance test takes kProofRel where wave_escaped takes kEscapeRel, and
+    // the proof is tried only where the magnitude guard holds for every lane of the wave. A wave gives
+    // up once a ray's bound step falls to kProofMinStep: what the proof tries changes no result.
     // Camera mode with the call's lattice (KArgs::lattice, march_policy). The soft ball needs spheres out of
     // the way in every direction; the lattice sees the gaps between them (once the optimizer has thrown a few
     // spheres outwards, R_soft covers all the rays thread through: profiles/r19_escape_lattice_sim.txt). It
@@ -553,21 +549,17 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
     // inside the lattice's cube, the soft ball alone outside it. G[cell] is the soft-min at the cell's centre
     // x_c (rm_lattice_kernel) and D is 1-Lipschitz, so D(p) >= D(x_c) - |p - x_c|: a point of the cell is at
     // most the half-diagonal h sqrt(3)/2 from x_c.
-    // Margins: slack = h sqrt(3)/2 (1 + 1e-4) + 1e-3 (write_bound), and the two 1e-3 of the soft ball on top (the
-    // march's and the bound step's). The 1e-4 relative covers the cell index: (e + half) / h is formed with
-    // three roundings, below 3e-7 N cells in all, so a point rounded into a neighbouring cell is within
-    // (1/2 + 2e-5) h of that cell's centre per axis. The 1e-3 covers the lattice kernel's fp32: its cell
-    // centres origin + i h (three roundings at magnitude <= B: 5e-5 per axis), its direct-form distances
-    // (one rounding of e at magnitude <= B, 3e-5; the square root and the sum 1e-6 relative of a distance
-    // below 2 B) and its logarithm (1e-6 / kappa). The maximum of two lower bounds is a lower bound; the
-    // give-up rule, the votes and steps_saved are the soft ball's. Array mode keeps the soft ball alone.
+    // Margins: the cell reader of rm_proof.h's ledger -- the slack write_bound formed (half-diagonal, cell
+    // index, the lattice kernel's fp32) and kBallAbs, the soft ball's two absolute allowances, on top. The
+    // maximum of two lower bounds is a lower bound; the give-up rule, the votes and steps_saved are the soft
+    // ball's. Array mode keeps the soft ball alone.
     static_assert((kLatticeN & (kLatticeN - 1)) == 0, "the inside test takes a power of two");
     auto bound_proof = [&](int st) {
       // a wave vote: origins differ per lane (array mode; a wave across two views), and every lane
       // takes part in the votes below and must leave with the same answer (dead is wave-uniform)
-      if (__any(!(onorm + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= 256.0f))) return false;
-      const float rs = (hdr[Hdr::kRsoft] + 1e-3f) * (1.0f + 1e-6f) + 1e-3f;
-      // the lattice's geometry (write_bound): half-side, 1 / h and the slack with the two 1e-3 of rs on top
+      if (__any(!(onorm + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= (float)kProofMaxMagnitude))) return false;
+      const float rs = (hdr[Hdr::kRsoft] + (float)kMarchAbs) * (1.0f + (float)kRadiusRel) + (float)kBoundStepAbs;
+      // the lattice's geometry (write_bound): half-side, 1 / h and the slack with rs's two absolute allowances on top
       const bool lat = CAM && a.lattice != nullptr && a.tile_proof == nullptr;
       float lat_half = 0.0f, lat_inv_h = 0.0f, lat_slack = 0.0f;
       if constexpr (CAM) {
@@ -575,7 +567,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
           const cf1_ptr lg = (cf1_ptr)RecLayout::at<const char>(a.rec_buf, RecLayout(a.Mpad).lattice());
           lat_half = lg[Lat::kHalf];
           lat_inv_h = lg[Lat::kInvH];
-          lat_slack = lg[Lat::kSlack] + 2e-3f;
+          lat_slack = lg[Lat::kSlack] + (float)kBallAbs;
         }
       }
       float u = t;
@@ -584,7 +576,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
         const float ex = fmaf(d[0], u, o[0]) - c0x, ey = fmaf(d[1], u, o[1]) - c0y, ez = fmaf(d[2], u, o[2]) - c0z;
         const float dist = fsqrt(fmaf(ez, ez, fmaf(ey, ey, ex * ex)));
         const float Tn = esc_tab[min(a.steps - n, kEscTab - 1)];
-        proven = proven || (fmaf(ez, d[2], fmaf(ey, d[1], ex * d[0])) >= 0.0f && dist * (1.0f - 2e-5f) >= Tn);
+        proven = proven || (fmaf(ez, d[2], fmaf(ey, d[1], ex * d[0])) >= 0.0f && dist * (1.0f - (float)kProofRel) >= Tn);
         if (__all(proven)) {
           steps_saved += a.steps - st;
           return true;

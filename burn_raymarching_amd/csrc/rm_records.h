@@ -230,20 +230,6 @@ __device__ __forceinline__ void scene_bound(const KArgs& a, float* scratch, int 
 // own rounded-up term, so v_j <= R and every exponent is <= 0; the sum (a term's relative error
 // below 2e-6 where it matters, at most M / 256 + 14 additions per chain) is taken 1e-5 up, the
 // logarithm's 1e-7 and the division go into the final 1e-5 relative + 1e-6. scratch as scene_bound's.
-// The escape proof runs from kProofMinSpheres (padded) spheres on: a bound step costs about a tenth
-// of a real march step at 64 spheres, and the C2 shape (256x256, 64 spheres, 10 views) ran 1.6 %
-// slower with the proof. A call without the proof (KArgs::proof, march_policy) launches the kernel
-// instance without it, and its record kernel skips the pass: R_soft = R + ln(M)/k, the ball's bound.
-constexpr int kProofMinSpheres = 128;
-// The escape lattice of the camera-mode proof (rm_tile_proof_kernel, bound_proof; KArgs::lattice): kLatticeN^3 cells over the cube
-// of half-side R' + kLatticeMargin about c_0. Sized by tools/escape_proof_sim.py on the bench scene after
-// 35 optimizer steps (profiles/r19_escape_lattice_sim.txt): 64 cells save 26.7 % of the march's packed
-// column blocks where the soft ball alone saves 2.9 %; 96 / 128 add 2 / 4 points for 3.4 / 8 times the fill
-// and a table of 3.5 / 8 MB against the 4 MB L2; the margin hardly matters (0.1 / 0.25 / 0.5: 27.0 / 26.7 / 25.7 %).
-constexpr int kLatticeN = 64;
-constexpr float kLatticeMargin = 0.25f;
-// the bound step at or below which a proof gives its wave up (bound_proof in rm_ray_kernel, rm_tile_proof_kernel)
-constexpr float kProofMinStep = 0.02f;
 __device__ __forceinline__ float soft_radius(const KArgs& a, float* scratch, int tid, const float c0[3], float R) {
   const int lane = tid & 63, wave = tid >> 6, nt = (int)blockDim.x, nw = nt >> 6;
   const float kappa = a.k * kLog2e;
@@ -268,8 +254,8 @@ __device__ __forceinline__ float soft_radius(const KArgs& a, float* scratch, int
 // Hdr::kCx..kR = the bounding sphere (c, R) of scene_bound, for the march's escape test, and its
 // distance thresholds T(n), n < kEscTab: a receding ray at distance d from c with n march steps
 // left ends them at distance >= gone_d + R' from c if (1 - 1e-5) d >= T(n). Every step is at
-// least g = d - R' long (R' = R + ln(M)/k + 1e-3: the soft-min is >= the hard min - ln(M)/k,
-// 1e-3 covers the fp32 march) and keeps the ray receding, so one step takes d to at least
+// least g = d - R' long (R' = proof_rprime: the soft-min is >= the hard min - ln(M)/k, kMarchAbs
+// covers the fp32 march; rm_proof.h) and keeps the ray receding, so one step takes d to at least
 // F(d) = (1 - 1e-5) sqrt(d^2 + (d - R')^2); T(0) = gone_d + R' and T(n) = F^-1(T(n - 1)) =
 // (R' + sqrt(2 y^2 - R'^2)) / 2 with y = T(n - 1) / (1 - 1e-5), rounded up. For n >= kEscTab the
 // march uses T(kEscTab - 1) >= T(n).
@@ -289,15 +275,15 @@ __device__ void write_bound(const KArgs& a, float* hdr, RecTail* tail) {
       // The escape lattice of this call (kLatticeN; rm_lattice_kernel fills it, rm_tile_proof_kernel or bound_proof reads it): the
       // cube of half-side R' + kLatticeMargin about c_0 in kLatticeN^3 cells of side h, cell i's centre at
       // -half + (i + 0.5) h per axis. The division is done here, once: the ray kernel multiplies by 1 / h.
-      // slack: the per-ray lookup's half-diagonal allowance, see bound_proof; the tile proof takes actual
-      // distances and does not read it.
-      const float half = (R + a.lse_slack + 1e-3f) * (1.0f + 1e-6f) + kLatticeMargin;
+      // slack: the per-ray lookup's half-diagonal allowance (the cell reader of rm_proof.h's ledger); the
+      // tile proof takes actual distances and does not read it.
+      const float half = proof_rprime(R, a.lse_slack) + kLatticeMargin;
       const float h = 2.0f * half / (float)kLatticeN;
       for (int k = 0; k < 3; ++k) tail->lat[Lat::kX0 + k] = (c[k] - half) + 0.5f * h;
       tail->lat[Lat::kH] = h;
       tail->lat[Lat::kHalf] = half;
       tail->lat[Lat::kInvH] = 1.0f / h;
-      tail->lat[Lat::kSlack] = h * (0.8660254f * (1.0f + 1e-4f)) + 1e-3f;
+      tail->lat[Lat::kSlack] = h * ((float)kLatticeHalfDiag * (1.0f + (float)kLatticeCellRel)) + (float)kLatticeKernelAbs;
       tail->lat[Lat::kZero] = 0.0f;
     }
   }
@@ -307,7 +293,7 @@ __device__ void write_bound(const KArgs& a, float* hdr, RecTail* tail) {
     // is conservative too: F^-1 grows with R' for y > R', which holds along the table.)
     float tv = INFINITY;
     if (a.gone_d > 0.0f) {
-      const float rp = (R + a.lse_slack + 1e-3f) * (1.0f + 1e-6f);
+      const float rp = proof_rprime(R, a.lse_slack);
       const float inv_shrink = 1.0000101f;  // y = T / (1 - 1e-5) <= T inv_shrink
       float T = (a.gone_d + rp) * (1.0f + 1e-6f);
       // four dependent instructions per step (v_sqrt_f32: 1 ulp, inside the round-up)

@@ -193,15 +193,15 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_lattice_kernel(co
 // plane, its central projection a convex spherical quadrilateral far inside a hemisphere about d_c, and the
 // distance from d_c is convex along great-circle arcs there, so it is largest at a corner. The corners are the
 // tile's own corner pixels' rays (camera_ray maps pixel x to x / W, not to its centre), in their fp32 bits;
-// the other rays' fp32 directions lie within 2e-7 of the exact quadrilateral, and delta is taken 1e-4
-// relative + 2e-6 up. With p_c(u) = o + d_c u, every ray has |p_r(u) - p_c(u)| <= |u| delta, and D is 1-Lipschitz:
+// the other rays' fp32 directions lie within 2e-7 of the exact quadrilateral, and delta is taken kTileConeRel
+// relative + kTileConeAbs up. With p_c(u) = o + d_c u, every ray has |p_r(u) - p_c(u)| <= |u| delta, and D is 1-Lipschitz:
 //   t_r + D(p_r(t_r)) >= u + D(p_r(u)) >= u + L(p_c(u)) - |u| delta        for u <= t_r, any L <= D,
 // so u <- u + L(p_c(u)) - |u| delta stays at or behind every ray's march step for step, as bound_proof's u does
 // for its own ray. The tile is proven at a bound step once wave_escaped's test holds at p_r(u) for every
 // r, in the conservative forms
-//   distance   |p_c - c_0| - |u| delta >= T(steps left) / (1 - 2e-5)        (|p_r - c_0| >= |p_c - c_0| - |u| delta)
-//   receding   (o - c_0) . d_c - |o - c_0| delta + u (1 -+ 2e-6) >= 0       ((p_r - c_0) . d_r = (o - c_0) . d_r + u |d_r|^2)
-// (the sign of the 2e-6 that makes the term smaller); the ray at t_r >= u is then receding and at least as far out.
+//   distance   |p_c - c_0| - |u| delta >= T(steps left) kProofDistUp             (|p_r - c_0| >= |p_c - c_0| - |u| delta)
+//   receding   (o - c_0) . d_c - |o - c_0| delta + u (1 -+ kTileRecedeRel) >= 0  ((p_r - c_0) . d_r = (o - c_0) . d_r + u |d_r|^2)
+// (the sign that makes the term smaller); the ray at t_r >= u is then receding and at least as far out.
 // The spare-lane alternative (the per-ray test, 64 lanes per tile) was not taken: one lane per tile is the point.
 //
 // The bound. L = max(|p - c_0| - R_soft, max over the 8 lattice points n around p of G[n] - |p - x_n|), less the
@@ -209,20 +209,16 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_lattice_kernel(co
 // cell-index rounding argument of a one-cell lookup are not needed, and no inside test either -- the base index
 // is held to [0, N - 2] per axis, and a far lattice point only gives a weak bound. x_n is formed as
 // rm_lattice_kernel forms it, origin + (float)i h in fp32 without contraction: the same bits, the point G[n] was
-// evaluated at. Margins. The pre-pass is latency-bound (one lane per tile: a 10-view call is 640 waves of it, each
-// a chain of up to S dependent bound steps), so a bound step is kept short. The cone's own state -- u, p_c, e,
-// the sums of squares, the tests -- runs in fp64 (contraction off), roundings below 1e-13 at the magnitudes the
-// guard B <= 256 admits. Its square roots are fp32 (v_sqrt_f32 of the fp64 sum rounded to fp32: 6e-8 + 1.2e-7
-// relative; no fp64 square root or division in the loop) and each is taken 1e-6 relative to the safe side: up
-// (sqrt_up; + 1e-15 for an argument fp32 flushes to 0) for |o - c_0| and delta, down (sqrt_down) for |p_c - c_0|,
-// which enters the bound step and the distance test from below. The lattice term is fp32 throughout: p rounded
-// to fp32 (1.5e-5 per axis at B), q = p - x_n (x_n exact: the lattice kernel's bits), the three squares summed,
-// the square root, g - |q| (1 + 2e-6): the relative 2e-6 covers the sum, the root and the last product (4e-7),
-// another 1e-4 absolute the rounding of p and of the difference g - |q| (below 6e-5 at B). The cell index is fp32
-// too and carries no margin: every lattice point gives a valid bound. What remains is what bound_proof
-// charges: R_soft's 1e-3 for the fp32 march of the real rays and 1e-3 per bound step, here on both terms
-// (2e-3), and 1e-3 on the lattice term for rm_lattice_kernel's fp32 (its direct-form distances, one rounding of
-// e at magnitude <= B, 3e-5; square root, sum and logarithm 1e-6 relative): 3.1e-3 in all on the lattice term.
+// evaluated at.
+// Margins: the tile reader of rm_proof.h's ledger. Specific to this reader: the pre-pass is latency-bound (one
+// lane per tile: a 10-view call is 640 waves of it, each a chain of up to S dependent bound steps), so a bound
+// step is kept short. The cone's own state -- u, p_c, e, the sums of squares, the tests -- runs in fp64
+// (contraction off), roundings below 1e-13 at the magnitudes the guard admits. Its square roots are fp32 (no fp64
+// square root or division in the loop), each taken kTileRootRel to the safe side: up (sqrt_up) for |o - c_0| and
+// delta, down (sqrt_down) for |p_c - c_0|, which enters the bound step and the distance test from below. The
+// lattice term is fp32 throughout: p rounded to fp32, q = p - x_n (x_n exact: the lattice kernel's bits), the
+// three squares summed, the square root, g - |q| (1 + kTileLatticeRel), less kTileLatticeAbs: what bound_proof
+// charges on both terms, the lattice kernel's fp32 and this reader's own rounding of p and of g - |q|.
 // The give-up rule is bound_proof's: a net bound step of kProofMinStep or less ends the tile's proof with 0.
 // Tiles that get 0 unseen: a tile whose 64 lanes are not all rays of the launch (none under tiling 2: a view is
 // whole 256-ray blocks), the magnitude guard. The host launches this kernel only for tiled launches large enough
@@ -230,8 +226,8 @@ __global__ __launch_bounds__(kBlock, kMinWavesPerSimd) void rm_lattice_kernel(co
 // those launches and the small ones read the lattice per ray inside bound_proof instead. A wave whose byte is 0
 // pays for the soft ball twice -- this trajectory's L held the soft-ball term already -- which keeps the taken
 // set a superset of the soft ball's by construction and costs such a wave one more soft-ball bound march.
-__device__ __forceinline__ double sqrt_up(double x) { return (double)fsqrt((float)x) * (1.0 + 1e-6) + 1e-15; }
-__device__ __forceinline__ double sqrt_down(double x) { return (double)fsqrt((float)x) * (1.0 - 1e-6); }
+__device__ __forceinline__ double sqrt_up(double x) { return (double)fsqrt((float)x) * (1.0 + kTileRootRel) + kTileRootFloor; }
+__device__ __forceinline__ double sqrt_down(double x) { return (double)fsqrt((float)x) * (1.0 - kTileRootRel); }
 __device__ __forceinline__ bool tile_proven(const KArgs& a, long long w) {
 #pragma clang fp contract(off)
   if (a.tiling != 2 || !(a.gone_d > 0.0f) || a.lattice == nullptr || 64 * w + 64 > a.n_rays) return false;
@@ -253,7 +249,7 @@ __device__ __forceinline__ bool tile_proven(const KArgs& a, long long w) {
   float o[3], dk[4][3];
   for (int k = 0; k < 4; ++k) camera_ray(cam, x0 + 7 * (k & 1), y0 + 7 * (k >> 1), a.width, a.height, o, dk[k]);
   // bound_proof's magnitude guard, in its fp32 form
-  if (!(fabsf(o[0]) + fabsf(o[1]) + fabsf(o[2]) + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= 256.0f))
+  if (!(fabsf(o[0]) + fabsf(o[1]) + fabsf(o[2]) + fabsf(c0x) + fabsf(c0y) + fabsf(c0z) + 3.0f * esc_tab[0] <= (float)kProofMaxMagnitude))
     return false;
   double dc[3];
   for (int k = 0; k < 3; ++k) dc[k] = ((double)dk[0][k] + (double)dk[1][k]) + ((double)dk[2][k] + (double)dk[3][k]);
@@ -265,13 +261,16 @@ __device__ __forceinline__ bool tile_proven(const KArgs& a, long long w) {
     const double ex = (double)dk[k][0] - dc[0], ey = (double)dk[k][1] - dc[1], ez = (double)dk[k][2] - dc[2];
     delta = fmax(delta, sqrt_up(ex * ex + ey * ey + ez * ez));
   }
-  delta = delta * (1.0 + 1e-4) + 2e-6;
+  delta = delta * (1.0 + kTileConeRel) + kTileConeAbs;
 
   const double c0[3] = {(double)c0x, (double)c0y, (double)c0z};
   const double oc[3] = {(double)o[0] - c0[0], (double)o[1] - c0[1], (double)o[2] - c0[2]};
   const double rec0 = (oc[0] * dc[0] + oc[1] * dc[1] + oc[2] * dc[2]) -
                       sqrt_up(oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2]) * delta;
-  const double rs = (double)((hdr[Hdr::kRsoft] + 1e-3f) * (1.0f + 1e-6f) + 1e-3f);  // bound_proof's rs
+  // bound_proof's rs: the same formula, compiled here without contraction, so the last bit may differ. Both are
+  // sound (allowances of 1e-3 against a rounding of 1e-7); the taken set is a superset of the soft ball's because
+  // a wave whose byte is 0 runs bound_proof, not because the bits agree
+  const double rs = (double)((hdr[Hdr::kRsoft] + (float)kMarchAbs) * (1.0f + (float)kRadiusRel) + (float)kBoundStepAbs);
   const float h = lg[Lat::kH], x0f[3] = {lg[Lat::kX0], lg[Lat::kY0], lg[Lat::kZ0]};
   const float half = lg[Lat::kHalf], inv_h = lg[Lat::kInvH];
 
@@ -291,7 +290,7 @@ __device__ __forceinline__ bool tile_proven(const KArgs& a, long long w) {
     const double dist = sqrt_down(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);  // enters both uses from below
     const double ud = fabs(u) * delta;
     const double Tn = (double)esc_tab[min(a.steps - n, kEscTab - 1)];
-    if (rec0 + u * (u >= 0.0 ? 1.0 - 2e-6 : 1.0 + 2e-6) >= 0.0 && dist - ud >= Tn * 1.0000200005) return true;  // >= Tn / (1 - 2e-5)
+    if (rec0 + u * (u >= 0.0 ? 1.0 - kTileRecedeRel : 1.0 + kTileRecedeRel) >= 0.0 && dist - ud >= Tn * kProofDistUp) return true;
     double Lb = dist - rs;
     // the lattice term, fp32: per axis the base index (>= 0: the conversion truncates as floor would) and the
     // squared offsets of p from the two lattice planes beside it; then the 8 points, one base address
@@ -314,9 +313,9 @@ __device__ __forceinline__ bool tile_proven(const KArgs& a, long long w) {
     for (int c = 0; c < 8; ++c) {
       const int jx = c & 1, jy = (c >> 1) & 1, jz = c >> 2;
       const float dn = fsqrt(q2[0][jx] + q2[1][jy] + q2[2][jz]);
-      best = fmaxf(best, fmaf(dn, -(1.0f + 2e-6f), g0[(jz * kLatticeN + jy) * kLatticeN + jx]));
+      best = fmaxf(best, fmaf(dn, -(1.0f + (float)kTileLatticeRel), g0[(jz * kLatticeN + jy) * kLatticeN + jx]));
     }
-    Lb = fmax(Lb, (double)best - 3.1e-3);
+    Lb = fmax(Lb, (double)best - kTileLatticeAbs);
     const double step = Lb - ud;
     if (!(step > (double)kProofMinStep)) return false;
     u += step;

@@ -5,12 +5,10 @@ cell-centre soft-min values. Exact: the train step with the lattice, with the so
 counters show what the lattice adds. The calls here are far below kLatticeMinRays, so the lattice is
 switched on by RM_PROOF_LATTICE=1 (the policy test leaves it unset). RM_SMALL=0 / RM_SPLIT=0: the
 general unsplit kernel, the proof's scope."""
-import numpy as np
 import pytest
 
 from conftest import gpu_available
-from test_escape_lattice_reference import (GAP_CAM, Geometry, cloud_scene, coincident_scene, gap_scene, outlier_scene,
-                                           wave_tiles)
+from escape_ref import CASES, GAP_CAM, _train, gap_scene, outlier_scene, wave_tiles
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
 
@@ -29,51 +27,6 @@ def general_kernel(monkeypatch):
     monkeypatch.setenv("RM_SPLIT", "0")
     monkeypatch.delenv("RM_PROOF_LATTICE", raising=False)
     monkeypatch.delenv("RM_NO_EARLY_EXIT", raising=False)
-
-
-def _plane_cams(sc, k):
-    """eye and target on a cell face of the lattice (y = a lattice plane): the central ray runs along it"""
-    g = Geometry(sc, k)
-    y = g.c0[1] - g.half + 40 * g.h
-    return [([g.c0[0] + 0.3, y, g.c0[2] + 2.5], [g.c0[0] - 0.5, y, g.c0[2]], 50.0)]
-
-
-TWO_BLOCK_CAM = ([0.0, 0.5, 2.5], [1.2, 0.5, 0.0], 40.0)
-
-FAR = np.array([29.0, -29.0, 29.0])  # 50.2 from the origin
-
-# name: (scene, cameras, (w, h), march steps, k)
-CASES = {
-    "beside": lambda: (cloud_scene(300), [([0.0, 0.5, 2.5], [2.2, 0.5, 0.0], 20.0)], (48, 80), 32, 32.0),
-    "gap": lambda: (gap_scene(128), [GAP_CAM], (48, 80), 32, 32.0),
-    "gap-two-views": lambda: (gap_scene(128), [GAP_CAM, ([0.3, 0.2, -2.6], [0.0, 0.0, 0.0], 30.0)], (64, 64), 32, 32.0),
-    "in-cube-outside-cloud": lambda: (cloud_scene(300), [([0.9, 0.35, 0.3], [0.0, 1.6, 0.0], 70.0)], (64, 64), 32, 32.0),
-    "inside-cloud": lambda: (cloud_scene(300), [([0.05, 0.0, -0.1], [1.0, 0.3, 0.2], 70.0)], (48, 80), 32, 32.0),
-    "far-from-origin": lambda: (cloud_scene(128, centre=FAR), [(list(FAR + [0.0, 0.5, 2.5]), list(FAR + [1.6, 0.5, 0.0]), 40.0)],
-                                (64, 64), 8, 32.0),
-    "one-centre": lambda: (coincident_scene(128), [([0.0, 0.3, 2.0], [0.6, 0.0, 0.0], 60.0)], (48, 80), 8, 5.0),
-    "outliers-k5": lambda: (outlier_scene(300), [([0.0, 0.5, 3.5], [2.0, 0.5, 0.0], 40.0)], (64, 64), 32, 5.0),
-    "lattice-plane": lambda: (outlier_scene(128), _plane_cams(outlier_scene(128), 32.0), (64, 64), 32, 32.0),
-    # 520 spheres: Mpad = 544, 272 pairs, two blocks of the record kernel -- the smallest scene whose record
-    # buffer has partial headers, so the lattice geometry (and every section behind the header) sits
-    # elsewhere than in the one-block cases above. The eye is "beside"'s, turned towards the cloud: at
-    # "beside" itself both proofs take all 60 waves.
-    "two-record-blocks": lambda: (cloud_scene(520), [TWO_BLOCK_CAM], (48, 80), 32, 32.0),
-}
-
-
-def _train(mods, sc, cams, w, h, S, k):
-    torch, _, render, _ = mods
-    tgt = torch.full((len(cams) * w * h, 3), 0.25, device="cuda")
-    out = torch.empty_like(tgt)
-    ctx = render.context()
-    ctx.stats(True)
-    ctx.collect_stats(reset=True)
-    loss, g, _ = render.train_step_camera(cams, w, h, tgt, sc, k, 0.5, S, out=out)
-    torch.cuda.synchronize()
-    st = ctx.collect_stats(reset=True)
-    ctx.stats(False)
-    return dict(loss=loss.clone(), out=out.clone(), **{key: v.clone() for key, v in g.items()}), st
 
 
 @pytest.fixture(scope="module")
@@ -128,7 +81,7 @@ def test_gap_scene_saves_more_and_exits_no_wave_that_shows(mods, runs, monkeypat
 
 
 def test_two_record_blocks_lattice_proves_strictly_more(mods, runs, monkeypatch):
-    """the 520-sphere case is not vacuous: test_escape_lattice_reference's CPU model (waves_taken) takes 55 of
+    """the 520-sphere case is not vacuous: the CPU model (escape_ref.waves_taken) takes 55 of
     this view's 60 waves with the lattice and 49 with the soft ball alone, so a kernel that read the lattice
     geometry from the wrong offset cannot pass by proving nothing"""
     res = runs("two-record-blocks", monkeypatch)[0]

@@ -15,10 +15,8 @@ import numpy as np
 import pytest
 
 from conftest import gpu_available
-from test_escape_lattice_reference import GAP_CAM, cloud_scene, gap_scene, outlier_scene
-from test_gpu_escape_lattice import CASES as LATTICE_CASES
-from test_gpu_escape_lattice import _train
-from test_tile_proof_reference import model_bytes
+from escape_ref import CASES as LATTICE_CASES
+from escape_ref import GAP_CAM, _train, cloud_scene, gap_scene, model_bytes, outlier_scene
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not gpu_available(), reason="needs a HIP device")]
 

@@ -1,19 +1,13 @@
-"""The tile proof of the camera-mode escape proof (rm_tile_proof_kernel in rm_sdf.h)
-restated in numpy float64, against the true soft-min and the fp32 oracle march.
+"""The tile proof of the camera-mode escape proof (rm_tile_proof_kernel in rm_sdf.h) as
+tests/escape_ref.py restates it (the tile reader: cone, bound, tile_proof; the formulas and the margins are at
+the top of that module), against the true soft-min and the fp32 oracle march.
 
-One bound trajectory per 8x8 pixel tile (a wave of the per-ray kernel). With the tile's four corner rays d_k
-(float32, the rays of the tile's own corner pixels), d_c their normalised sum and
-delta = max_k |d_k - d_c| (1 + 1e-4) + 2e-6, every ray r of the tile has |d_r - d_c| <= delta, and with
-p_c(u) = o + d_c u, e = p_c - c_0:
-
-    L(p)   = max(|e| - R_soft - 2e-3, max over the 8 lattice points n around p of G[n] - |p - x_n| (1 + 2e-6) - 3.1e-3)
-    u     <- u + L(p_c(u)) - |u| delta                        (given up at a net step <= kProofMinStep)
-    proven: (o - c_0) . d_c - |o - c_0| delta + u (1 - 2e-6) >= 0  and  |e| - |u| delta >= T(steps left) / (1 - 2e-5)
-
-x_n = origin + (float)i h in float32, the point G[n] was evaluated at; the base index is held to [0, N - 2], no
-inside test (D(p) >= D(x_n) - |p - x_n| holds for every lattice point). As in the kernel, the cone's state is
-float64, its square roots float32 taken 1e-6 to the safe side (sqrt_up, sqrt_down) and the lattice term float32
-throughout. The scenes, views and the oracle march are test_escape_lattice_reference's.
+One bound trajectory per 8x8 pixel tile (a wave of the per-ray kernel): with the tile's four corner rays d_k
+(float32, the rays of the tile's own corner pixels), d_c their normalised sum and delta of cone(), every ray r
+of the tile has |d_r - d_c| <= delta. The mutants: the step without |u| delta or with the previous step's u in
+it, the cone built from the pixel centres, the lattice points taken half a cell from where G was evaluated, and
+the receding test on the centre ray alone. The scenes, views and the oracle march are escape_ref's, computed once
+for this module and test_escape_lattice_reference.
 
 Counts of the restated proofs on the GPU test's views (tests/test_gpu_tile_proof.py), 48x80, 60 waves each:
 gap scene 50 waves by the cone, 0 by the soft ball, 50 by the per-ray one-cell lattice proof this one replaces;
@@ -23,124 +17,20 @@ the 520-sphere scene 55 by the cone, 49 by the soft ball, 55 by the per-ray latt
 import numpy as np
 import pytest
 
-from test_escape_proof_reference import soft_min
-from test_escape_lattice_reference import (GAP_CAM, MIN_STEP, N, SCENES, VIEWS, Geometry, cloud_scene, gap_scene,  # noqa: F401
-                                           guard_ok, marched, oracle_march, sampled, view_rays, wave_tiles, waves_taken)
-
-F = np.float32
-CORNERS = [0, 7, 56, 63]  # of an 8x8 tile in row order: the tile's extreme rays
-
-
-# ---- the restatement -------------------------------------------------------------------------
-
-def sqrt_up(x):
-    """the kernel's square roots are fp32, each taken 1e-6 relative to the safe side"""
-    return np.sqrt(np.asarray(x, np.float64).astype(F)).astype(np.float64) * (1 + 1e-6) + 1e-15
-
-
-def sqrt_down(x):
-    return np.sqrt(np.asarray(x, np.float64).astype(F)).astype(np.float64) * (1 - 1e-6)
-
-
-def lattice_bound(g, p, plus_half=True):
-    """the lattice term of L at points p [n, 3] (float64): max over the 8 lattice points around p"""
-    p = np.asarray(p, np.float64)
-    e = (p - g.c0).astype(F)
-    f = np.clip((e + F(g.half)) * F(g.inv_h) - F(0.5), F(0), F(N - 2))  # float32, as the kernel's: any index is valid
-    i0 = f.astype(np.int64)
-    best = np.full(len(p), -np.inf, F)
-    idx = np.concatenate([i0 + np.array([c & 1, (c >> 1) & 1, c >> 2]) for c in range(8)])
-    uniq, inv = np.unique(idx, axis=0, return_inverse=True)
-    G = g.cell_values(uniq)[inv.reshape(-1)].reshape(8, len(p))
-    for c in range(8):
-        xn = g.centres(idx[c * len(p):(c + 1) * len(p)], plus_half)  # float32: G's own points unless mutated
-        q = p.astype(F) - xn
-        q2 = q * q
-        dn = np.sqrt((q2[:, 0] + q2[:, 1]) + q2[:, 2])
-        best = np.maximum(best, G[c] - dn * F(1 + 2e-6))
-    return best.astype(np.float64) - 3.1e-3
-
-
-def bound(g, p, **mutant):
-    """L(p) and its soft-ball term"""
-    ball = sqrt_down(((np.asarray(p, np.float64) - g.c0) ** 2).sum(1)) - g.rs
-    return np.maximum(ball, lattice_bound(g, p, **mutant)), ball
-
-
-def cone(d4, delta_scale=1.0):
-    """(d_c, delta) of tiles with corner rays d4 [tiles, 4, 3] (float32)"""
-    d4 = d4.astype(np.float64)
-    dc = (d4[:, 0] + d4[:, 1]) + (d4[:, 2] + d4[:, 3])
-    dc *= (F(1) / np.sqrt((dc * dc).sum(1).astype(F))).astype(np.float64)[:, None]  # an fp32 reciprocal square root
-    delta = sqrt_up(((d4 - dc[:, None, :]) ** 2).sum(2)).max(1)
-    return dc, delta_scale * delta * (1 + 1e-4) + 2e-6
-
-
-def tile_proof(g, eye, d4, u0, st0=1, lattice=True, drop_ud=False, delta_scale=1.0, plus_half=True, stale_ud=False,
-               centre_recedes=False):
-    """rm_tile_proof_kernel for tiles of one view: (taken [tiles]; u at the top of every bound step [S + 1, tiles],
-    nan where the tile's bound march has ended; the step at which a taken tile was proven). The keyword
-    arguments after `lattice` are the mutants."""
-    S = g.S
-    eye = np.asarray(eye, F).astype(np.float64)
-    dc, delta = cone(d4, delta_scale)
-    nt = len(dc)
-    oc = eye - g.c0
-    rec0 = dc @ oc - (0.0 if centre_recedes else sqrt_up((oc * oc).sum())) * delta
-    ok = np.abs(eye).sum() + np.abs(g.c0).sum() + 3.0 * g.T[0] <= 256.0
-    u = np.full(nt, float(u0))
-    u_prev = u.copy()
-    run = np.full(nt, bool(ok))
-    taken = np.zeros(nt, bool)
-    at = np.full(nt, -1)
-    traj = np.full((S + 1, nt), np.nan)
-    for n in range(st0, S):
-        if not run.any():
-            break
-        traj[n, run] = u[run]
-        p = eye + dc * u[:, None]
-        dist = sqrt_down(((p - g.c0) ** 2).sum(1))
-        ud = np.abs(u_prev if stale_ud else u) * delta
-        proven = run & (rec0 + u * np.where(u >= 0, 1 - 2e-6, 1 + 2e-6) >= 0) & (dist - ud >= g.T[S - n] * 1.0000200005)
-        taken |= proven
-        at[proven] = n
-        run &= ~proven
-        Lb = dist - g.rs
-        if lattice and run.any():
-            Lb[run] = np.maximum(Lb[run], lattice_bound(g, p[run], plus_half))
-        step = Lb - (0.0 if drop_ud else ud)
-        run &= step > MIN_STEP
-        u_prev = u.copy()
-        u = np.where(run, u + step, u)
-    return taken, traj, at
-
-
-def shared_t1(m_t1, o, d, g):
-    """the t every ray of a view that is not gone at the eye has after the origin step"""
-    e = o[0].astype(np.float64) - g.c0
-    gone0 = (d.astype(np.float64) @ e >= 0) & (np.linalg.norm(e) * (1 - 1e-5) >= g.T[g.S])
-    live = np.flatnonzero(~gone0)
-    return (m_t1[live[0]] if len(live) else m_t1[0]), gone0
-
-
-FAR_VIEW = ([0.0, 0.5, 12.0], [0.0, 0.0, 0.0], 90.0)  # a far eye, a wide field: the rays turn to receding at different u
+import escape_ref
+from escape_ref import (BALL_ABS, CORNERS, ESCAPE_REL, F, FAR_VIEW, GAP_CAM, PROOF_REL, SCENES, VIEWS, Geometry, bound,
+                        cloud_scene, cone, gap_scene, lattice_bound, model_taken, soft_min, tile_proof, view_rays,
+                        wave_tiles, waves_taken)
 
 
 @pytest.fixture(scope="module")
-def cones(oracle, marched):  # noqa: F811
-    """per marched view of test_escape_lattice_reference, and a far wide one: the tile proof of its 16 tiles"""
-    out = list(marched)
-    sc = cloud_scene(300)
-    g = Geometry(sc, 32.0, 32)
-    o, d = view_rays(oracle, 32, 32, FAR_VIEW)
-    out.append(dict(kind="far", M=300, k=32.0, S=32, g=g, o=o, d=d, t=oracle_march(oracle, o, d, sc, 32, 32.0),
-                    mask=np.asarray(oracle.render_diff_debug(o, d, sc, 32, 32.0, "f32")[:, 10])))
-    tiles = wave_tiles(32, 32)
-    for m in out:
-        m["tiles"] = tiles
-        m["d4"] = m["d"][tiles[:, CORNERS]]
-        m["t1"], m["gone0"] = shared_t1(m["t"][1], m["o"], m["d"], m["g"])
-    return out
+def sampled():
+    return escape_ref.sampled()
+
+
+@pytest.fixture(scope="module")
+def cones(oracle):
+    return escape_ref.cones(oracle)
 
 
 def _run(m, **mutant):
@@ -149,7 +39,7 @@ def _run(m, **mutant):
 
 # ---- the bound ---------------------------------------------------------------------------------
 
-def test_neighbour_bound_is_below_the_soft_min(sampled):  # noqa: F811
+def test_neighbour_bound_is_below_the_soft_min(sampled):
     tight = 0
     for kind, M, k, g, p, D in sampled:
         assert len(p) == 100000
@@ -159,14 +49,14 @@ def test_neighbour_bound_is_below_the_soft_min(sampled):  # noqa: F811
     assert tight > 100000  # not vacuous: at a quarter of the points the lattice term is the larger
 
 
-def test_neighbour_bound_beats_the_cell_bound(sampled):  # noqa: F811
+def test_neighbour_bound_beats_the_cell_bound(sampled):
     """what the 8 actual distances buy over the one cell's half-diagonal slack, inside the cube"""
     for kind, M, k, g, p, D in sampled[:2]:
         inside = (np.abs(p - g.c0) < g.half - g.h).all(1)
-        assert np.mean(lattice_bound(g, p[inside]) + 2e-3 >= g.bound(p[inside])[0]) > 0.99
+        assert np.mean(lattice_bound(g, p[inside]) + BALL_ABS >= g.bound(p[inside])[0]) > 0.99
 
 
-def test_centres_offset_by_half_a_cell_break_the_bound(sampled):  # noqa: F811
+def test_centres_offset_by_half_a_cell_break_the_bound(sampled):
     """mutant 3: the distance taken to a lattice point half a cell from where G was evaluated"""
     bad = 0
     for kind, M, k, g, p, D in sampled:
@@ -260,7 +150,7 @@ def _proofs_without_the_test(m, **mutant):
         idx = m["tiles"][w]
         d = m["d"][idx].astype(np.float64)
         e = m["o"][idx].astype(np.float64) + d * traj[at[w], w] - g.c0
-        ok = ((e * d).sum(1) >= 0) & (np.linalg.norm(e, axis=1) * (1 - 2e-5) >= g.T[g.S - at[w]])
+        ok = ((e * d).sum(1) >= 0) & (np.linalg.norm(e, axis=1) * (1 - PROOF_REL) >= g.T[g.S - at[w]])
         bad += int(not ok.all())
     return bad, int(taken.sum())
 
@@ -289,7 +179,7 @@ def test_no_false_proofs(cones):
         gone = np.zeros(len(o), bool)
         for n in range(S + 1):
             e = o + d * m["t"][n].astype(np.float64)[:, None] - g.c0
-            gone |= ((e * d).sum(-1) >= 0) & (np.linalg.norm(e, axis=1) * (1 - 1e-5) >= g.T[S - n])
+            gone |= ((e * d).sum(-1) >= 0) & (np.linalg.norm(e, axis=1) * (1 - ESCAPE_REL) >= g.T[S - n])
         taken = _run(m)[0]
         for w in np.flatnonzero(taken):
             idx = m["tiles"][w]
@@ -299,27 +189,6 @@ def test_no_false_proofs(cones):
 
 
 # ---- the views of tests/test_gpu_tile_proof.py ----------------------------------------------------
-
-def model_bytes(oracle, sc, cam, w, h, S, k):
-    """the kernel's byte per tile of one view, in wave_tiles(w, h)'s order, and the view's rays and their t after
-    the origin step"""
-    g = Geometry(sc, k, S)
-    o, d = view_rays(oracle, w, h, cam)
-    t1 = np.asarray(oracle.render_diff(o, d, sc, 1, k, precision="f32", with_t=True)[1], F)
-    tiles = wave_tiles(w, h)
-    u0, gone0 = shared_t1(t1, o, d, g)
-    return tile_proof(g, o[0], d[tiles[:, CORNERS]], u0)[0], (g, o, d, t1, tiles, gone0)
-
-
-def model_taken(oracle, sc, cam, w, h, S, k):
-    """(tiles the cone takes, tiles the soft-ball proof takes, tiles the per-ray lattice proof took) of one view,
-    as index sets over wave_tiles(w, h); a tile whose rays are all gone at the eye counts for none"""
-    taken, (g, o, d, t1, tiles, gone0) = model_bytes(oracle, sc, cam, w, h, S, k)
-    ball = waves_taken(g, o, d, t1, tiles, lattice=False)[0]
-    ray = waves_taken(g, o, d, t1, tiles)[0]
-    keep = set(np.flatnonzero(~gone0[tiles].all(1)))
-    return set(np.flatnonzero(taken)) & keep, set(ball) & keep, set(ray) & keep
-
 
 def test_counts_on_the_gpu_views(oracle):
     """not vacuous: the gap view and the 520-sphere view of the GPU test, where the cone must take strictly more
