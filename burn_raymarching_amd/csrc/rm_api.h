@@ -123,6 +123,36 @@ int check_sdf_params(rm_context* ctx, const rm_sdf_params* params, rm_sdf_params
   return RM_OK;
 }
 
+// the coefficients of the rm_render_diff_sh calls
+int check_sh(rm_context* ctx, const float* sh, int32_t sh_degree) {
+  if (sh_degree < 0 || sh_degree > RM_SH_MAX_DEGREE)
+    return fail(ctx, RM_ERR_INVALID_ARG, "sh_degree %d out of [0, %d]", sh_degree, RM_SH_MAX_DEGREE);
+  if (sh_degree > 0 && !sh) return fail(ctx, RM_ERR_INVALID_ARG, "sh is NULL with sh_degree %d", sh_degree);
+  return RM_OK;
+}
+
+ShCall sh_forward_call(const Geometry& g, const float* sh, int degree, float* out, float* t_march) {
+  ShCall c(g);
+  c.sh = sh;
+  c.degree = degree;
+  c.out = out;
+  c.t_out = t_march;
+  return c;
+}
+
+ShCall sh_backward_call(const Geometry& g, const float* sh, int degree, const float* grad_out, const float* t_march,
+                        const rm_grads* grads, float* grad_sh, int accumulate) {
+  ShCall c(g);
+  c.sh = sh;
+  c.degree = degree;
+  c.gout = grad_out;
+  c.t_in = t_march;
+  if (grads) c.want = *grads;
+  c.grad_sh = grad_sh;
+  c.accumulate = accumulate;
+  return c;
+}
+
 }  // namespace
 
 extern "C" {
@@ -678,6 +708,54 @@ int rm_render_diff_backward_cameras(rm_context* ctx, const rm_camera* cams, int3
   c.grad_cams = grad_cams;
   c.accumulate = accumulate;
   return run_raygrad(ctx, c);
+}
+
+int rm_render_diff_sh(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
+                      const rm_scene* scene, const float* sh, int32_t sh_degree, const rm_march* march, float* out,
+                      float* t_march) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  int rc;
+  if ((rc = check_sh(ctx, sh, sh_degree)) != RM_OK) return rc;
+  if (sh_degree == 0) return rm_render_diff(ctx, ray_org, ray_dir, num_rays, scene, march, out, t_march);
+  return run_sh_forward(ctx, sh_forward_call(ray_geometry(ray_org, ray_dir, num_rays, scene, march), sh, sh_degree, out, t_march));
+}
+
+int rm_render_diff_sh_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width, int32_t height,
+                             const rm_scene* scene, const float* sh, int32_t sh_degree, const rm_march* march,
+                             float* out, float* t_march) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  int rc;
+  if ((rc = check_sh(ctx, sh, sh_degree)) != RM_OK) return rc;
+  if (sh_degree == 0) return rm_render_diff_camera(ctx, cams, num_views, width, height, scene, march, out, t_march);
+  return run_sh_forward(ctx, sh_forward_call(camera_geometry(cams, num_views, width, height, scene, march), sh, sh_degree, out,
+                                             t_march));
+}
+
+int rm_render_diff_sh_backward(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
+                               const rm_scene* scene, const float* sh, int32_t sh_degree, const rm_march* march,
+                               const float* grad_out, const float* t_march, const rm_grads* grads, float* grad_sh,
+                               int32_t accumulate) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  int rc;
+  if ((rc = check_sh(ctx, sh, sh_degree)) != RM_OK) return rc;
+  if (sh_degree == 0)
+    return rm_render_diff_backward(ctx, ray_org, ray_dir, num_rays, scene, march, grad_out, t_march, grads, accumulate);
+  return run_sh_backward(ctx, sh_backward_call(ray_geometry(ray_org, ray_dir, num_rays, scene, march), sh, sh_degree, grad_out,
+                                               t_march, grads, grad_sh, accumulate));
+}
+
+int rm_render_diff_sh_backward_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width,
+                                      int32_t height, const rm_scene* scene, const float* sh, int32_t sh_degree,
+                                      const rm_march* march, const float* grad_out, const float* t_march,
+                                      const rm_grads* grads, float* grad_sh, int32_t accumulate) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  int rc;
+  if ((rc = check_sh(ctx, sh, sh_degree)) != RM_OK) return rc;
+  if (sh_degree == 0)
+    return rm_render_diff_backward_camera(ctx, cams, num_views, width, height, scene, march, grad_out, t_march, grads,
+                                          accumulate);
+  return run_sh_backward(ctx, sh_backward_call(camera_geometry(cams, num_views, width, height, scene, march), sh, sh_degree,
+                                               grad_out, t_march, grads, grad_sh, accumulate));
 }
 
 void rm_view_params_default(rm_view_params* p) {

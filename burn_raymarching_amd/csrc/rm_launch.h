@@ -1,7 +1,9 @@
 // rm_launch.h -- launch orchestration behind the C ABI: what a call is (Geometry, Call,
 // RayGradCall), its checks and its KArgs, and the launch sequences of the general kernel (run),
 // the small-scene kernel (run_small), the ray-gradient kernel (run_raygrad), the viewer's frame
-// render (run_view), the distance-field query (run_sdf), its backward (run_sdf_grad) and the gradient reduction. Host code only; included by rm_kernels.hip after rm_context.h.
+// render (run_view), the distance-field query (run_sdf), its backward (run_sdf_grad), the view-dependent
+// colour's forward and backward (run_sh_forward, run_sh_backward) and the gradient reduction. Host code only;
+// included by rm_kernels.hip after rm_context.h.
 #pragma once
 
 namespace {
@@ -1331,6 +1333,168 @@ int run_sdf_grad(rm_context* ctx, const float* points, long long n, const rm_sce
     hipExtLaunchKernelGGL(rm_sdf_grad_kernel, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream, ev0, ev1, 0u, s);
     RM_HIP(ctx, hipGetLastError());
     if (want != nullptr && (rc = reduce_and_finalize(ctx, c, a, nb, done == 0)) != RM_OK) return rc;
+    done += nb * kBlock;
+  }
+  return RM_OK;
+}
+
+// ---- view-dependent colour (rm_sh.h) ---------------------------------------------------------
+
+// rm_render_diff_sh[_camera] and their backward: the rays and the scene, the coefficients (degree 1 or 2:
+// degree 0 is the existing entry point and never gets here) and the outputs of either direction.
+struct ShCall : Geometry {
+  const float* sh = nullptr;
+  int degree = 0;
+  float* out = nullptr;    // forward
+  float* t_out = nullptr;  // forward, nullable
+  const float* gout = nullptr;  // backward
+  const float* t_in = nullptr;  // backward, nullable: the existing forward replays the march
+  rm_grads want{};              // backward: the scene gradient's members to write
+  float* grad_sh = nullptr;     // backward, nullable
+  int accumulate = 0;
+  explicit ShCall(const Geometry& g) : Geometry(g) {}
+  int cols() const { return 3 * ((degree + 1) * (degree + 1) - 1); }  // 3B
+};
+
+// The march of an SH call: the existing forward (every kernel path and march flag) writes t for all rays.
+int sh_march(rm_context* ctx, const ShCall& c, float* t) {
+  Call f(kFwd, c);
+  f.t_out = t;
+  return run(ctx, f);
+}
+
+// The KArgs of the SH kernels (the march fields stay zero: they start from t_in), the call's records and its
+// packed coefficients.
+int sh_prepare(rm_context* ctx, const ShCall& c, KArgs& a, ShArgs& s) {
+  int rc;
+  std::memset(&a, 0, sizeof a);
+  std::memset(&s, 0, sizeof s);
+  fill_scene_args(c, a);
+  if ((rc = fill_camera_args(ctx, c, a)) != RM_OK) return rc;
+  if ((rc = prepare_records(ctx, a, false)) != RM_OK) return rc;
+  const int np = a.Mpad / 2, cols = c.cols();
+  if ((rc = ctx->sh_rec.ensure(ctx, sizeof(float2) * (size_t)np * cols, "coefficient records")) != RM_OK) return rc;
+  hipLaunchKernelGGL(rm_sh_pack_kernel, dim3((unsigned)((np * cols + 255) / 256)), dim3(256), 0, ctx->stream, c.sh, a.M, np,
+                     cols, ctx->sh_rec.as<float2>());
+  RM_HIP(ctx, hipGetLastError());
+  s.shp = ctx->sh_rec.as<const f2v>();
+  return RM_OK;
+}
+
+int run_sh_forward(rm_context* ctx, const ShCall& c) {
+  ctx->opt_prepared = false;
+  int rc;
+  if ((rc = check_geometry(ctx, c, true)) != RM_OK) return rc;
+  const long long n = c.rays();
+  if (n > 0 && !c.out && !c.t_out) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
+  if (n == 0) return RM_OK;
+  float* t = c.t_out;
+  if (!t) {
+    if ((rc = ctx->rg_ws.ensure(ctx, rg_need(n), "ray-gradient workspace")) != RM_OK) return rc;
+    t = ctx->rg_ws.as<float>();
+  }
+  if ((rc = sh_march(ctx, c, t)) != RM_OK || !c.out) return rc;
+  KArgs a;
+  ShArgs s;
+  if ((rc = sh_prepare(ctx, c, a, s)) != RM_OK) return rc;
+  a.t_in = t;
+  a.out = c.out;
+  for (long long done = 0; done < n;) {
+    const long long nb = std::min<long long>((n - done + kBlock - 1) / kBlock, max_blocks_per_launch());
+    a.ray_begin = done;
+    a.n_rays = std::min<long long>(n - done, nb * kBlock);
+    hipEvent_t ev0, ev1;
+    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
+    const dim3 gr((unsigned)nb), blk(kBlock);
+    if (c.cam && c.degree == 1) hipExtLaunchKernelGGL((rm_sh_shade_kernel<true, 3>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, a, s);
+    else if (c.cam) hipExtLaunchKernelGGL((rm_sh_shade_kernel<true, 8>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, a, s);
+    else if (c.degree == 1) hipExtLaunchKernelGGL((rm_sh_shade_kernel<false, 3>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, a, s);
+    else hipExtLaunchKernelGGL((rm_sh_shade_kernel<false, 8>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, a, s);
+    RM_HIP(ctx, hipGetLastError());
+    done += nb * kBlock;
+  }
+  return RM_OK;
+}
+
+// Blocks of 256 rays per backward launch: the sub-launch limit, and no more than keep the per-sphere part of
+// the launch's partial records (8 + 3B floats a sphere) within kSdfGradScratch bytes of the workspace.
+long long sh_grad_blocks_per_launch(int Mpad, int cols) {
+  const long long fit = (long long)(kSdfGradScratch / (sizeof(float) * (size_t)(8 + cols) * (size_t)Mpad));
+  return std::max<long long>(1, std::min<long long>(fit, max_blocks_per_launch()));
+}
+
+// The coefficient gradient of a launch of nb blocks: rm_sh_reduce_partials + rm_sh_finalize on its records.
+int sh_reduce(rm_context* ctx, const KArgs& a, const ShArgs& s, int cols, long long nb, float* S, float* grad_sh,
+              int accumulate) {
+  const int stride = a.Mpad * cols, seg_len = (int)((nb + kShSegs - 1) / kShSegs);
+  hipLaunchKernelGGL(rm_sh_reduce_partials, dim3((unsigned)((stride + 255) / 256), (unsigned)kShSegs), dim3(256), 0,
+                     ctx->stream, s.gsh_part, stride, a.partials + (long long)a.Mpad * 8 + 7, a.rec, (int)nb, seg_len, S);
+  RM_HIP(ctx, hipGetLastError());
+  hipLaunchKernelGGL(rm_sh_finalize, dim3((unsigned)((a.M * cols + 255) / 256)), dim3(256), 0, ctx->stream, S, stride,
+                     a.M * cols, grad_sh, accumulate);
+  RM_HIP(ctx, hipGetLastError());
+  return RM_OK;
+}
+
+int run_sh_backward(rm_context* ctx, const ShCall& c) {
+  ctx->opt_prepared = false;
+  int rc;
+  if ((rc = check_geometry(ctx, c, true)) != RM_OK) return rc;
+  const bool scene_grad = c.want.centers || c.want.colors || c.want.radius || c.want.light_dir || c.want.ambient;
+  if (!scene_grad && !c.grad_sh) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
+  const long long n = c.rays();
+  if (n > 0 && !c.gout) return fail(ctx, RM_ERR_INVALID_ARG, "grad_out is NULL");
+  if (n == 0 && c.accumulate) return RM_OK;
+  const float* t_in = c.t_in;
+  if (n > 0 && !t_in) {  // no saved t: the existing forward replays the march into the workspace
+    if ((rc = ctx->rg_ws.ensure(ctx, rg_need(n), "ray-gradient workspace")) != RM_OK) return rc;
+    if ((rc = sh_march(ctx, c, ctx->rg_ws.as<float>())) != RM_OK) return rc;
+    t_in = ctx->rg_ws.as<float>();
+  }
+  KArgs a;
+  ShArgs s;
+  if (n > 0) {
+    if ((rc = sh_prepare(ctx, c, a, s)) != RM_OK) return rc;
+  } else {  // no records: the reductions need M and the record sizes only
+    std::memset(&a, 0, sizeof a);
+    std::memset(&s, 0, sizeof s);
+    fill_scene_args(c, a);
+  }
+  a.gout = c.gout;
+  a.t_in = t_in;
+  // the workspace: main partial records | their segment sums | coefficient records | their segment sums
+  const int cols = c.cols();
+  const long long per = sh_grad_blocks_per_launch(a.Mpad, cols);
+  const long long nbmax = std::max<long long>(1, std::min<long long>((n + kBlock - 1) / kBlock, per));
+  const long long main_floats = nbmax * a.rec + (long long)reduce_segs(nbmax) * a.rec + 4096;
+  const long long rec_sh = (long long)a.Mpad * cols;
+  if ((rc = ctx->ws.ensure(ctx, (size_t)(main_floats + (nbmax + kShSegs) * rec_sh) * sizeof(float), "workspace")) != RM_OK)
+    return rc;
+  a.partials = ctx->ws.as<float>();
+  s.gsh_part = a.partials + main_floats;
+  float* S_sh = s.gsh_part + nbmax * rec_sh;
+  Call red(kBwd, c);  // the main record's reduction: the per-ray kernels', unchanged
+  red.grads = &c.want;
+  red.accumulate = c.accumulate;
+  if (n == 0) {  // every requested element: zero
+    if (scene_grad && (rc = reduce_and_finalize(ctx, red, a, 0, true)) != RM_OK) return rc;
+    return c.grad_sh ? sh_reduce(ctx, a, s, cols, 0, S_sh, c.grad_sh, 0) : RM_OK;
+  }
+  for (long long done = 0; done < n;) {
+    const long long nb = std::min<long long>((n - done + kBlock - 1) / kBlock, per);
+    a.ray_begin = done;
+    a.n_rays = std::min<long long>(n - done, nb * kBlock);
+    hipEvent_t ev0, ev1;
+    if ((rc = next_events(ctx, ev0, ev1)) != RM_OK) return rc;
+    const dim3 gr((unsigned)nb), blk(kBlock);
+    if (c.cam && c.degree == 1) hipExtLaunchKernelGGL((rm_sh_grad_kernel<true, 3>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, a, s);
+    else if (c.cam) hipExtLaunchKernelGGL((rm_sh_grad_kernel<true, 8>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, a, s);
+    else if (c.degree == 1) hipExtLaunchKernelGGL((rm_sh_grad_kernel<false, 3>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, a, s);
+    else hipExtLaunchKernelGGL((rm_sh_grad_kernel<false, 8>), gr, blk, 0, ctx->stream, ev0, ev1, 0u, a, s);
+    RM_HIP(ctx, hipGetLastError());
+    const bool first = done == 0;
+    if (scene_grad && (rc = reduce_and_finalize(ctx, red, a, nb, first)) != RM_OK) return rc;
+    if (c.grad_sh && (rc = sh_reduce(ctx, a, s, cols, nb, S_sh, c.grad_sh, first ? c.accumulate : 1)) != RM_OK) return rc;
     done += nb * kBlock;
   }
   return RM_OK;

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("RM_LIB_PATH") or os.path.join(_PKG, "lib", "libraymar
 
 RM_OK = 0
 RM_MAX_VIEWS_PER_CALL = 128
+RM_SH_MAX_DEGREE = 2
 _ERR_NAMES = {1: "RM_ERR_INVALID_ARG", 2: "RM_ERR_HIP", 3: "RM_ERR_OOM", 4: "RM_ERR_UNSUPPORTED"}
 
 _P = ctypes.c_void_p
@@ -98,6 +99,15 @@ SIGNATURES = {
     "rm_render_diff_backward_cameras": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32,
                                                        ctypes.POINTER(RmScene), ctypes.POINTER(RmMarch), _P, _P,
                                                        _P, _I32]),
+    "rm_render_diff_sh": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(RmScene), _P, _I32, ctypes.POINTER(RmMarch),
+                                         _P, _P]),
+    "rm_render_diff_sh_camera": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32, ctypes.POINTER(RmScene),
+                                                _P, _I32, ctypes.POINTER(RmMarch), _P, _P]),
+    "rm_render_diff_sh_backward": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.POINTER(RmScene), _P, _I32,
+                                                  ctypes.POINTER(RmMarch), _P, _P, ctypes.POINTER(RmGrads), _P, _I32]),
+    "rm_render_diff_sh_backward_camera": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32,
+                                                         ctypes.POINTER(RmScene), _P, _I32, ctypes.POINTER(RmMarch), _P,
+                                                         _P, ctypes.POINTER(RmGrads), _P, _I32]),
     "rm_train_step": (ctypes.c_int, [_P, _P, _P, _P, _I64, _F, _F, ctypes.POINTER(RmScene),
                                      ctypes.POINTER(RmMarch), ctypes.POINTER(RmGrads), _P, _P, _I32]),
     "rm_train_step_camera": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32, _P, _F, _F,

@@ -9,6 +9,10 @@ Names and argument meaning follow the reference:
   * ``render_diff_cameras(eye, target, fov_deg, width, height, ...)`` -- the same as an autograd
     function over the camera tensors too (pose refinement; rm_render_diff_backward_cameras), and
     ``render_diff_backward_rays`` / ``render_diff_backward_cameras`` -- the ray / pose gradients;
+  * ``render_diff_sh(ray_org, ray_dir, centers, colors, sh, radius, ...)`` -- render_diff with a
+    view-dependent colour per sphere, spherical harmonics of degree 1 or 2 over the base colour
+    (rm_render_diff_sh / rm_render_diff_sh_backward; ``render_diff_sh_forward`` / ``_backward`` and
+    their ``_camera`` forms are the calls themselves);
   * ``train_step(...)`` -- forward + compute_loss reconstruction seed + backward fused;
   * ``create_camera_rays(width, height, eye, target, fov_deg)`` -- host ray
     generation (camera.rs:30-90, a host loop in the reference too);
@@ -377,6 +381,176 @@ def render_diff_backward_camera(cams, width, height, scene: Scene, smooth_k, gra
                                                       _ptr(grad_out), _ptr(t_march), ctypes.byref(cg), 0),
               "rm_render_diff_backward_camera")
     return g
+
+
+# ---- view-dependent sphere colour: spherical harmonics (rm_render_diff_sh) ---------------------
+SH_BANDS = {0: 0, 3: 1, 8: 2}  # coefficients per sphere and channel -> degree
+
+
+def _sh_coeffs(sh, m):
+    """(contiguous float32 [M, B, 3] tensor, degree) of the coefficients; B must be 0, 3 or 8."""
+    if not isinstance(sh, torch.Tensor) or sh.dim() != 3 or sh.shape[0] != m or sh.shape[2] != 3:
+        raise ValueError(f"sh must be a [M, B, 3] tensor with M = {m}")
+    if sh.shape[1] not in SH_BANDS:
+        raise ValueError(f"sh has {sh.shape[1]} coefficients per sphere and channel: 0, 3 (degree 1) or 8 (degree 2)")
+    if sh.shape[1] == 0:
+        return None, 0
+    return _f32(sh, (m, sh.shape[1], 3), "sh"), SH_BANDS[sh.shape[1]]
+
+
+def _sh_march(scene, smooth_k, steps, normal_eps, color_sharpness, mask_sharpness, flags):
+    return scene.march_for(native.march_params(steps, smooth_k, normal_eps, color_sharpness, mask_sharpness, flags=flags))
+
+
+def _sh_outputs(scene, sh, want):
+    """Output tensors and the (rm_grads, grad_sh) arguments for the gradients named in `want`."""
+    dev, m = scene.centers.device, scene.num_spheres
+    shapes = {"centers": (m, 3), "colors": (m, 3), "radius": (m,), "light_dir": (3,), "ambient": (1,)}
+    if sh is not None:
+        shapes["sh"] = tuple(sh.shape)
+    unknown = [k for k in want if k not in shapes]
+    if unknown:
+        raise ValueError(f"unknown gradient {unknown[0]!r}")
+    g = {k: torch.empty(shapes[k], device=dev) for k in want}
+    cg = RmGrads(*[g[k].data_ptr() if k in g else None for k in ("centers", "colors", "radius", "light_dir", "ambient")])
+    return g, cg, _ptr(g.get("sh"))
+
+
+SH_GRADS = ("centers", "colors", "radius", "light_dir", "ambient", "sh")
+
+
+def render_diff_sh_forward(ray_org, ray_dir, scene: Scene, sh, smooth_k, steps=40, *, normal_eps=1e-4,
+                           color_sharpness=10.0, mask_sharpness=15.0, return_t=False, flags=0):
+    """rm_render_diff_sh: render_diff with the albedo max(col_j + sum_b sh[j][b] Y_b(d / |d|), 0) per sphere
+    and ray (sh: [M, B, 3], B = 3 or 8; B = 0 is render_diff itself). out [N, 3], and t_march [N] if asked."""
+    n = ray_org.shape[0]
+    ray_org = _f32(ray_org, (n, 3), "ray_org")
+    ray_dir = _f32(ray_dir, (n, 3), "ray_dir")
+    sh, deg = _sh_coeffs(sh, scene.num_spheres)
+    out = torch.empty((n, 3), device=ray_org.device)
+    t = torch.empty((n,), device=ray_org.device) if return_t else None
+    ctx = context(ray_org.device)
+    march = _sh_march(scene, smooth_k, steps, normal_eps, color_sharpness, mask_sharpness, flags)
+    ctx.check(ctx._lib.rm_render_diff_sh(ctx.handle, _ptr(ray_org), _ptr(ray_dir), n, ctypes.byref(scene.c_struct()),
+                                         _ptr(sh), deg, ctypes.byref(march), _ptr(out), _ptr(t)), "rm_render_diff_sh")
+    return (out, t) if return_t else out
+
+
+def render_diff_sh_backward(ray_org, ray_dir, scene: Scene, sh, smooth_k, grad_out, steps=40, *, t_march=None,
+                            want=SH_GRADS, normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0, flags=0):
+    """rm_render_diff_sh_backward: the gradients of sum(out * grad_out) named in `want` (centers, colors,
+    radius, light_dir, ambient, sh), as a dict of float32 tensors. Deterministic: two calls give the same bits."""
+    n = ray_org.shape[0]
+    ray_org = _f32(ray_org, (n, 3), "ray_org")
+    ray_dir = _f32(ray_dir, (n, 3), "ray_dir")
+    grad_out = _f32(grad_out, (n, 3), "grad_out")
+    if t_march is not None:
+        t_march = _f32(t_march, (n,), "t_march")
+    sh, deg = _sh_coeffs(sh, scene.num_spheres)
+    g, cg, gsh = _sh_outputs(scene, sh, want)
+    ctx = context(ray_org.device)
+    march = _sh_march(scene, smooth_k, steps, normal_eps, color_sharpness, mask_sharpness, flags)
+    ctx.check(ctx._lib.rm_render_diff_sh_backward(ctx.handle, _ptr(ray_org), _ptr(ray_dir), n,
+                                                  ctypes.byref(scene.c_struct()), _ptr(sh), deg, ctypes.byref(march),
+                                                  _ptr(grad_out), _ptr(t_march), ctypes.byref(cg), gsh, 0),
+              "rm_render_diff_sh_backward")
+    return g
+
+
+def render_diff_sh_camera(cams, width, height, scene: Scene, sh, smooth_k, steps=40, *, normal_eps=1e-4,
+                          color_sharpness=10.0, mask_sharpness=15.0, return_t=False, flags=0):
+    """rm_render_diff_sh_camera: render_diff_sh_forward over in-kernel camera rays, out [V*H*W, 3] (up to
+    128 views a call)."""
+    cams = list(cams)
+    if not 1 <= len(cams) <= native.RM_MAX_VIEWS_PER_CALL:
+        raise ValueError(f"1..{native.RM_MAX_VIEWS_PER_CALL} views per call")
+    n = len(cams) * width * height
+    dev = scene.centers.device
+    sh, deg = _sh_coeffs(sh, scene.num_spheres)
+    out = torch.empty((n, 3), device=dev)
+    t = torch.empty((n,), device=dev) if return_t else None
+    ctx = context(dev)
+    march = _sh_march(scene, smooth_k, steps, normal_eps, color_sharpness, mask_sharpness, flags)
+    ctx.check(ctx._lib.rm_render_diff_sh_camera(ctx.handle, native.cameras(cams), len(cams), width, height,
+                                                ctypes.byref(scene.c_struct()), _ptr(sh), deg, ctypes.byref(march),
+                                                _ptr(out), _ptr(t)), "rm_render_diff_sh_camera")
+    return (out, t) if return_t else out
+
+
+def render_diff_sh_backward_camera(cams, width, height, scene: Scene, sh, smooth_k, grad_out, steps=40, *, t_march=None,
+                                   want=SH_GRADS, normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0, flags=0):
+    """rm_render_diff_sh_backward_camera: render_diff_sh_backward over in-kernel camera rays."""
+    cams = list(cams)
+    if not 1 <= len(cams) <= native.RM_MAX_VIEWS_PER_CALL:
+        raise ValueError(f"1..{native.RM_MAX_VIEWS_PER_CALL} views per call")
+    n = len(cams) * width * height
+    grad_out = _f32(grad_out, (n, 3), "grad_out")
+    if t_march is not None:
+        t_march = _f32(t_march, (n,), "t_march")
+    sh, deg = _sh_coeffs(sh, scene.num_spheres)
+    g, cg, gsh = _sh_outputs(scene, sh, want)
+    ctx = context(scene.centers.device)
+    march = _sh_march(scene, smooth_k, steps, normal_eps, color_sharpness, mask_sharpness, flags)
+    ctx.check(ctx._lib.rm_render_diff_sh_backward_camera(ctx.handle, native.cameras(cams), len(cams), width, height,
+                                                         ctypes.byref(scene.c_struct()), _ptr(sh), deg,
+                                                         ctypes.byref(march), _ptr(grad_out), _ptr(t_march),
+                                                         ctypes.byref(cg), gsh, 0),
+              "rm_render_diff_sh_backward_camera")
+    return g
+
+
+class _RenderDiffShFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, ray_org, ray_dir, centers, colors, sh, radius, light_dir, ambient, smooth_k, steps, normal_eps,
+                color_sharpness, mask_sharpness):
+        scene = Scene(centers.detach(), colors.detach(), radius.detach(), light_dir.detach(), ambient.detach())
+        ctx.consts = {"normal_eps": normal_eps, "color_sharpness": color_sharpness, "mask_sharpness": mask_sharpness}
+        shd = sh.detach()
+        out, t = render_diff_sh_forward(ray_org.detach(), ray_dir.detach(), scene, shd, smooth_k, steps, return_t=True,
+                                        **ctx.consts)
+        ctx.save_for_backward(ray_org, ray_dir, t, shd)
+        ctx.scene = scene
+        ctx.smooth_k = smooth_k
+        ctx.steps = steps
+        ctx.radius_shape = radius.shape
+        ctx.ambient_shape = ambient.shape
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        ray_org, ray_dir, t, sh = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        names = ("centers", "colors", "sh", "radius", "light_dir", "ambient")
+        want = [k for k, w in zip(names, need[2:8]) if w and not (k == "sh" and sh.shape[1] == 0)]
+        g = {}
+        if want:
+            g = render_diff_sh_backward(ray_org, ray_dir, ctx.scene, sh, ctx.smooth_k, grad_out.contiguous().float(),
+                                        ctx.steps, t_march=t, want=want, **ctx.consts)
+        if need[4] and sh.shape[1] == 0:
+            g["sh"] = torch.zeros_like(sh)
+        gr, ga = g.get("radius"), g.get("ambient")
+        return (None, None, g.get("centers"), g.get("colors"), g.get("sh"),
+                gr.reshape(ctx.radius_shape) if gr is not None else None, g.get("light_dir"),
+                ga.reshape(ctx.ambient_shape) if ga is not None else None, None, None, None, None, None)
+
+
+def render_diff_sh(ray_org, ray_dir, centers, colors, sh, radius, light_dir, ambient, smooth_k, steps=40, *,
+                   normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0):
+    """render_diff with view-dependent sphere colour: each sphere's albedo on a ray of direction d is
+    max(colors_j + sum_b sh[j][b] Y_b(d / |d|), 0), Y the real spherical harmonics of degree 1 (sh [M, 3, 3])
+    or 2 (sh [M, 8, 3]) with 3D Gaussian splatting's constants and signs; sh [M, 0, 3] is render_diff.
+    Differentiable w.r.t. centers, colors, sh, radius, light_dir and ambient (rm_render_diff_sh_backward, from
+    the forward's saved march t; only the gradients whose inputs require grad are computed). The rays are
+    not: Y's dependence on the direction is not differentiated, so rays that require grad raise."""
+    if not isinstance(sh, torch.Tensor) or sh.dim() != 3 or sh.shape[1] not in SH_BANDS:
+        got = tuple(sh.shape) if isinstance(sh, torch.Tensor) else type(sh).__name__
+        raise ValueError(f"sh must be [M, B, 3] with B = 0, 3 (degree 1) or 8 (degree 2), got {got}")
+    if any(isinstance(r, torch.Tensor) and r.requires_grad for r in (ray_org, ray_dir)):
+        raise ValueError("ray gradients are not available with SH: render_diff_sh does not differentiate ray_org / "
+                         "ray_dir (detach them, or use render_diff for the ray and pose gradients)")
+    return _RenderDiffShFn.apply(ray_org, ray_dir, centers, colors, sh, radius, light_dir, ambient, float(smooth_k),
+                                 int(steps), float(normal_eps), float(color_sharpness), float(mask_sharpness))
 
 
 def train_step(ray_org, ray_dir, targets, scene: Scene, smooth_k, progress, steps=40, *, inv_count=None,

@@ -272,6 +272,52 @@ int rm_render_diff_backward_cameras(rm_context* ctx, const rm_camera* cams, int3
                                     const float* grad_out, const float* t_march, rm_camera* grad_cams,
                                     int32_t accumulate);
 
+/* ---- view-dependent sphere colour: spherical harmonics --------------------- */
+/* render_diff with a colour per sphere AND ray direction. B = (sh_degree + 1)^2 - 1 (3 or 8); sh is
+ * DEVICE memory, fp32 [M, B, 3], sh[(j*B + b)*3 + c]; degree 0 is scene->colors. For a ray of
+ * direction d, u = d / |d| (a zero direction gives Y = 0) and, with the real SH constants and signs of
+ * 3D Gaussian splatting,
+ *   C1 = 0.4886025119029199
+ *   Y_1..3 = -C1 u.y,  C1 u.z,  -C1 u.x
+ *   C2 = {1.0925484305920792, -1.0925484305920792, 0.31539156525252005,
+ *         -1.0925484305920792, 0.5462742152960396}
+ *   Y_4..8 = C2[0] xy,  C2[1] yz,  C2[2] (2zz - xx - yy),  C2[3] xz,  C2[4] (xx - yy)
+ * the albedo of sphere j on that ray is a_jc = max(col_jc + sum_b sh[j][b][c] Y_b(u), 0) -- the clamp
+ * per sphere and per channel -- and everything else is render_diff (renderer_diff.rs:6-91) with the
+ * colours replaced by a, t and the normal detached:
+ *   mix_c = sum_j w_j a_jc,  w = softmax(-color_sharpness delta),   out = mix L mu.
+ * With g = dL/dout, gm = g L mu and mg = gm . mix the backward returns
+ *   dL/dcol_jc = w_j gm_c [a_jc > 0],   dL/dsh[j][b][c] = w_j gm_c Y_b [a_jc > 0],
+ * the colour term of dL/ddelta_j is -color_sharpness w_j (gm . a_j - mg), and the mask, reconnect,
+ * light and ambient terms are rm_render_diff_backward's with this mix. Y depends on the ray
+ * direction; that dependence is not differentiated (there is no ray or pose gradient with SH).
+ * sh_degree == 0: sh and grad_sh are ignored and the call IS the existing entry point, bit for bit.
+ * sh_degree outside 0..RM_SH_MAX_DEGREE, or sh NULL with sh_degree > 0: RM_ERR_INVALID_ARG.
+ * The march is the existing kernels' (every march flag applies to it); out comes from a shade
+ * kernel of its own that starts from the march's t. t_march: a nullable output of the forward, a
+ * nullable input of the backward (NULL: the march is replayed). RM_MARCH_COLOR_F16 is honoured for
+ * scene->colors; sh and grad_sh are always fp32.
+ * Backward: grads is nullable, as is each of its members and grad_sh ([M, B, 3], DEVICE); at least
+ * one output is required. accumulate as in rm_render_diff_backward: without it every element of
+ * every requested output is overwritten (num_rays == 0: with zeros). Rays whose backward seeds are
+ * zero (every escaped ray) add exact zeros. No floating-point atomics: two calls give the same
+ * bits, and an output's bits do not depend on which other outputs are requested. */
+#define RM_SH_MAX_DEGREE 2
+int rm_render_diff_sh(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
+                      const rm_scene* scene, const float* sh, int32_t sh_degree, const rm_march* march,
+                      float* out, float* t_march);
+int rm_render_diff_sh_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width,
+                             int32_t height, const rm_scene* scene, const float* sh, int32_t sh_degree,
+                             const rm_march* march, float* out, float* t_march);
+int rm_render_diff_sh_backward(rm_context* ctx, const float* ray_org, const float* ray_dir, int64_t num_rays,
+                               const rm_scene* scene, const float* sh, int32_t sh_degree, const rm_march* march,
+                               const float* grad_out, const float* t_march, const rm_grads* grads,
+                               float* grad_sh, int32_t accumulate);
+int rm_render_diff_sh_backward_camera(rm_context* ctx, const rm_camera* cams, int32_t num_views, int32_t width,
+                                      int32_t height, const rm_scene* scene, const float* sh, int32_t sh_degree,
+                                      const rm_march* march, const float* grad_out, const float* t_march,
+                                      const rm_grads* grads, float* grad_sh, int32_t accumulate);
+
 /* ---- fused train step: forward + compute_loss seed + backward ------------- */
 /* The reconstruction term of compute_loss (training.rs:17-34): for each ray,
  * W = 10 where sum(target) > 0.01 else 1 + 4*progress, loss += sum_c |out-target|*W,
