@@ -2,7 +2,7 @@
 
   burn_raymarching_amd/lib/libraymarch_hip.so  <- csrc/rm_kernels.hip   (the product: C ABI of include/raymarch.h;
                                                   one translation unit: the kernels in rm_kernels.hip and
-                                                  rm_{device,records,ray,reduce,small,raygrad,view,sdf,sh}.h, the host side in
+                                                  rm_{device,records,ray,reduce,small,raygrad,view,sdf,sh,loss}.h, the host side in
                                                   rm_{context,launch,api}.h)
   burn_raymarching_amd/lib/librm_host.so        <- csrc/host/{io,data,driver,comm,mesh}.cpp (C ABI of include/rm_host.h; RCCL)
   burn_raymarching_amd/lib/rm_train             <- csrc/host/main.cpp    (CLI: train / generate / preview / view / mesh)
@@ -47,7 +47,7 @@ KERNEL_SOURCES = [os.path.join(CSRC, "rm_kernels.hip"), os.path.join(CSRC, "rm_d
                   os.path.join(CSRC, "rm_proof.h"), os.path.join(CSRC, "rm_records.h"),
                   os.path.join(CSRC, "rm_reduce.h"), os.path.join(CSRC, "rm_small.h"),
                   os.path.join(CSRC, "rm_raygrad.h"), os.path.join(CSRC, "rm_view.h"),
-                  os.path.join(CSRC, "rm_sdf.h"), os.path.join(CSRC, "rm_sh.h"),
+                  os.path.join(CSRC, "rm_sdf.h"), os.path.join(CSRC, "rm_sh.h"), os.path.join(CSRC, "rm_loss.h"),
                   os.path.join(CSRC, "rm_ray.h"),
                   os.path.join(CSRC, "rm_context.h"),
                   os.path.join(CSRC, "rm_launch.h"), os.path.join(CSRC, "rm_api.h"),

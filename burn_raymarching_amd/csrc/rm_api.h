@@ -758,6 +758,24 @@ int rm_render_diff_sh_backward_camera(rm_context* ctx, const rm_camera* cams, in
                                                grad_out, t_march, grads, grad_sh, accumulate));
 }
 
+void rm_image_loss_default(rm_image_loss_params* p) {
+  if (!p) return;
+  p->l1_weight = 0.8f;    // 3D Gaussian splatting's lambda = 0.2
+  p->ssim_weight = 0.2f;
+  p->progress = 0.0f;
+  p->c1 = 1e-4f;          // 0.01^2
+  p->c2 = 9e-4f;          // 0.03^2
+  p->flags = 0;
+}
+
+int rm_image_loss(rm_context* ctx, const float* out, const float* targets, int32_t num_views, int32_t width,
+                  int32_t height, float inv_count, const rm_image_loss_params* params, float* loss, float* view_stats,
+                  float* ssim_map, float* grad_out) {
+  if (!ctx) return RM_ERR_INVALID_ARG;
+  return run_image_loss(ctx, out, targets, num_views, width, height, inv_count, params, loss, view_stats, ssim_map,
+                        grad_out);
+}
+
 void rm_view_params_default(rm_view_params* p) {
   if (!p) return;
   p->max_steps = 100;          // shader.wgsl MAX_STEPS

@@ -50,6 +50,7 @@ struct rm_context {
   DevBuf rg_ws;         // ray-gradient calls: march t [rays] | per-view partial rows (rm_raygrad_kernel)
   DevBuf rec;           // sphere records of the current call (rm_prep_kernel)
   DevBuf sh_rec;        // rm_render_diff_sh: the call's coefficients per sphere pair (rm_sh_pack_kernel)
+  DevBuf loss_ws;       // rm_image_loss: per-view fp64 sums | tile partial records | the A, B, C maps (rm_loss.h)
   DevBuf batch;         // rm_train_iteration's unfused path: the drawn batch (9 floats/ray)
   DevBuf cont_buf;      // split continuation: saved march state | list | count
   DevBuf stats_dev;     // work counters (rm_stats_enable), kStatsWords words

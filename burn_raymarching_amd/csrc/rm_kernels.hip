@@ -1114,6 +1114,7 @@ __global__ __launch_bounds__(kBlock) void rm_escape_kernel(const KArgs a, int* _
 #include "rm_view.h"
 #include "rm_sdf.h"
 #include "rm_sh.h"
+#include "rm_loss.h"
 
 // rm_debug_stall: one wave that holds its stream until the host sets *flag (a system-scope load
 // of host-mapped memory, polled with s_sleep) or max_ticks of the 100 MHz real-time counter have

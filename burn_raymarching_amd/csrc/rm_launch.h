@@ -2,7 +2,8 @@
 // RayGradCall), its checks and its KArgs, and the launch sequences of the general kernel (run),
 // the small-scene kernel (run_small), the ray-gradient kernel (run_raygrad), the viewer's frame
 // render (run_view), the distance-field query (run_sdf), its backward (run_sdf_grad), the view-dependent
-// colour's forward and backward (run_sh_forward, run_sh_backward) and the gradient reduction. Host code only;
+// colour's forward and backward (run_sh_forward, run_sh_backward), the image-space loss (run_image_loss) and the
+// gradient reduction. Host code only;
 // included by rm_kernels.hip after rm_context.h.
 #pragma once
 
@@ -1496,6 +1497,100 @@ int run_sh_backward(rm_context* ctx, const ShCall& c) {
     if (scene_grad && (rc = reduce_and_finalize(ctx, red, a, nb, first)) != RM_OK) return rc;
     if (c.grad_sh && (rc = sh_reduce(ctx, a, s, cols, nb, S_sh, c.grad_sh, first ? c.accumulate : 1)) != RM_OK) return rc;
     done += nb * kBlock;
+  }
+  return RM_OK;
+}
+
+// ---- the image-space loss (rm_loss.h) --------------------------------------------------------
+
+// [b, b + n) floats against [a, a + n)
+bool loss_overlap(const float* a, const float* b, long long n) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b, bytes = (uintptr_t)n * sizeof(float);
+  return a && b && pa < pb + bytes && pb < pa + bytes;
+}
+
+int run_image_loss(rm_context* ctx, const float* out, const float* targets, int num_views, int width, int height,
+                   float inv_count, const rm_image_loss_params* params, float* loss, float* view_stats, float* ssim_map,
+                   float* grad_out) {
+  ctx->opt_prepared = false;
+  rm_image_loss_params p;
+  rm_image_loss_default(&p);
+  if (params) p = *params;
+  if (!out) return fail(ctx, RM_ERR_INVALID_ARG, "out is NULL");
+  if (!targets) return fail(ctx, RM_ERR_INVALID_ARG, "targets is NULL");
+  if (num_views < 1) return fail(ctx, RM_ERR_INVALID_ARG, "num_views %d < 1", num_views);
+  if (width < 1) return fail(ctx, RM_ERR_INVALID_ARG, "width %d < 1", width);
+  if (height < 1) return fail(ctx, RM_ERR_INVALID_ARG, "height %d < 1", height);
+  if (!std::isfinite(inv_count)) return fail(ctx, RM_ERR_INVALID_ARG, "inv_count is not finite");
+  if (!(std::isfinite(p.l1_weight) && p.l1_weight >= 0.0f))
+    return fail(ctx, RM_ERR_INVALID_ARG, "l1_weight %g: finite and >= 0 required", (double)p.l1_weight);
+  if (!(std::isfinite(p.ssim_weight) && p.ssim_weight >= 0.0f))
+    return fail(ctx, RM_ERR_INVALID_ARG, "ssim_weight %g: finite and >= 0 required", (double)p.ssim_weight);
+  if (!std::isfinite(p.progress)) return fail(ctx, RM_ERR_INVALID_ARG, "progress is not finite");
+  if (!(std::isfinite(p.c1) && p.c1 > 0.0f)) return fail(ctx, RM_ERR_INVALID_ARG, "c1 %g: finite and > 0 required", (double)p.c1);
+  if (!(std::isfinite(p.c2) && p.c2 > 0.0f)) return fail(ctx, RM_ERR_INVALID_ARG, "c2 %g: finite and > 0 required", (double)p.c2);
+  if ((p.flags & ~RM_LOSS_PLAIN_L1) != 0) return fail(ctx, RM_ERR_INVALID_ARG, "flags 0x%x: RM_LOSS_PLAIN_L1 only", p.flags);
+  if (!loss && !view_stats && !ssim_map && !grad_out) return fail(ctx, RM_ERR_INVALID_ARG, "no output requested");
+  const long long n = 3LL * num_views * height * width;  // floats of an image array
+  if (loss_overlap(out, grad_out, n) || loss_overlap(targets, grad_out, n))
+    return fail(ctx, RM_ERR_INVALID_ARG, "grad_out aliases out or targets");
+  if (loss_overlap(out, ssim_map, n) || loss_overlap(targets, ssim_map, n))
+    return fail(ctx, RM_ERR_INVALID_ARG, "ssim_map aliases out or targets");
+  if (loss_overlap(grad_out, ssim_map, n)) return fail(ctx, RM_ERR_INVALID_ARG, "ssim_map aliases grad_out");
+
+  LossArgs a;
+  std::memset(&a, 0, sizeof a);
+  a.x = out;
+  a.y = targets;
+  a.H = height;
+  a.W = width;
+  a.tiles_x = (width + kLossTW - 1) / kLossTW;
+  a.tiles_y = (height + kLossTH - 1) / kLossTH;
+  const long long tpv = (long long)a.tiles_x * a.tiles_y, nblocks = tpv * num_views;
+  if (nblocks > INT32_MAX) return fail(ctx, RM_ERR_INVALID_ARG, "num_views x width x height: %lld tiles exceed one launch", nblocks);
+  a.c1 = p.c1;
+  a.c2 = p.c2;
+  a.progress = p.progress;
+  a.plain_l1 = (p.flags & RM_LOSS_PLAIN_L1) ? 1 : 0;
+  a.l1_scale = p.l1_weight * inv_count;
+  a.ssim_scale = -p.ssim_weight * inv_count;
+  const bool ssim_grad = grad_out && a.ssim_scale != 0.0f;
+  const bool stats = loss || view_stats || ssim_map || ssim_grad;
+
+  // the context's scratch: per-view sums (double) | tile partial records | A | B | C
+  const size_t sums_bytes = ((sizeof(double) * 3 * (size_t)num_views + 15) / 16) * 16;
+  const size_t part_bytes = sizeof(float) * kLossPart * (size_t)nblocks;
+  const size_t need = sums_bytes + part_bytes + (ssim_grad ? 3 * sizeof(float) * (size_t)n : 0);
+  int rc;
+  if ((rc = ctx->loss_ws.ensure(ctx, need, "image-loss scratch")) != RM_OK) return rc;
+  char* base = ctx->loss_ws.as<char>();
+  double* vsum = reinterpret_cast<double*>(base);
+  a.partials = reinterpret_cast<float*>(base + sums_bytes);
+  if (ssim_grad) {
+    a.A = reinterpret_cast<float*>(base + sums_bytes + part_bytes);
+    a.B = a.A + n;
+    a.C = a.B + n;
+  }
+  a.S = ssim_map;
+  a.grad = grad_out;
+  const dim3 grid((unsigned)nblocks), blk(kLossThreads);
+  if (stats) {
+    hipLaunchKernelGGL(rm_loss_stats_kernel, grid, blk, 0, ctx->stream, a);
+    RM_HIP(ctx, hipGetLastError());
+  }
+  if (loss || view_stats) {
+    hipLaunchKernelGGL(rm_loss_view_sums, dim3((unsigned)num_views), dim3(64), 0, ctx->stream, a.partials, (int)tpv, vsum,
+                       view_stats);
+    RM_HIP(ctx, hipGetLastError());
+  }
+  if (loss) {
+    hipLaunchKernelGGL(rm_loss_total, dim3(1), dim3(64), 0, ctx->stream, vsum, num_views, (double)n, p.l1_weight,
+                       p.ssim_weight, inv_count, loss);
+    RM_HIP(ctx, hipGetLastError());
+  }
+  if (grad_out) {
+    hipLaunchKernelGGL(rm_loss_grad_kernel, grid, blk, 0, ctx->stream, a);
+    RM_HIP(ctx, hipGetLastError());
   }
   return RM_OK;
 }

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("RM_LIB_PATH") or os.path.join(_PKG, "lib", "libraymar
 RM_OK = 0
 RM_MAX_VIEWS_PER_CALL = 128
 RM_SH_MAX_DEGREE = 2
+RM_LOSS_PLAIN_L1 = 1
 _ERR_NAMES = {1: "RM_ERR_INVALID_ARG", 2: "RM_ERR_HIP", 3: "RM_ERR_OOM", 4: "RM_ERR_UNSUPPORTED"}
 
 _P = ctypes.c_void_p
@@ -72,6 +73,10 @@ class RmSdfParams(ctypes.Structure):
     _fields_ = [("smooth_k", _F), ("color_sharpness", _F), ("flags", _I32)]
 
 
+class RmImageLossParams(ctypes.Structure):
+    _fields_ = [("l1_weight", _F), ("ssim_weight", _F), ("progress", _F), ("c1", _F), ("c2", _F), ("flags", _I32)]
+
+
 class RmGrads(ctypes.Structure):
     _fields_ = [("centers", _P), ("colors", _P), ("radius", _P), ("light_dir", _P), ("ambient", _P)]
 
@@ -113,6 +118,9 @@ SIGNATURES = {
     "rm_train_step_camera": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32, _P, _F, _F,
                                             ctypes.POINTER(RmScene), ctypes.POINTER(RmMarch),
                                             ctypes.POINTER(RmGrads), _P, _P, _I32]),
+    "rm_image_loss_default": (None, [ctypes.POINTER(RmImageLossParams)]),
+    "rm_image_loss": (ctypes.c_int, [_P, _P, _P, _I32, _I32, _I32, _F, ctypes.POINTER(RmImageLossParams), _P, _P, _P,
+                                     _P]),
     "rm_render": (ctypes.c_int, [_P, _P, _P, _I64, _P, _P, _P, _I32, _P]),
     "rm_render_camera": (ctypes.c_int, [_P, ctypes.POINTER(RmCamera), _I32, _I32, _I32, _P, _P, _P, _I32, _P]),
     "rm_view_params_default": (None, [ctypes.POINTER(RmViewParams)]),
@@ -322,6 +330,18 @@ def sdf_params(**kw) -> RmSdfParams:
     for k, v in kw.items():
         if k not in dict(RmSdfParams._fields_):
             raise TypeError(f"rm_sdf_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def image_loss_params(**kw) -> RmImageLossParams:
+    """rm_image_loss_params with rm_image_loss_default's values (weights 0.8 / 0.2, progress 0, c1 = 1e-4,
+    c2 = 9e-4, no flags); keyword arguments override fields."""
+    p = RmImageLossParams()
+    lib().rm_image_loss_default(ctypes.byref(p))
+    for k, v in kw.items():
+        if k not in dict(RmImageLossParams._fields_):
+            raise TypeError(f"rm_image_loss_params has no field {k!r}")
         setattr(p, k, v)
     return p
 

@@ -13,6 +13,9 @@ Names and argument meaning follow the reference:
     view-dependent colour per sphere, spherical harmonics of degree 1 or 2 over the base colour
     (rm_render_diff_sh / rm_render_diff_sh_backward; ``render_diff_sh_forward`` / ``_backward`` and
     their ``_camera`` forms are the calls themselves);
+  * ``image_loss(out, target, width, height)`` -- weighted L1 + D-SSIM on whole rendered views as an
+    autograd scalar over ``out``, and ``image_metrics`` -- PSNR / SSIM / L1 per view (rm_image_loss;
+    ``image_loss_call`` is the call itself);
   * ``train_step(...)`` -- forward + compute_loss reconstruction seed + backward fused;
   * ``create_camera_rays(width, height, eye, target, fov_deg)`` -- host ray
     generation (camera.rs:30-90, a host loop in the reference too);
@@ -551,6 +554,109 @@ def render_diff_sh(ray_org, ray_dir, centers, colors, sh, radius, light_dir, amb
                          "ray_dir (detach them, or use render_diff for the ray and pose gradients)")
     return _RenderDiffShFn.apply(ray_org, ray_dir, centers, colors, sh, radius, light_dir, ambient, float(smooth_k),
                                  int(steps), float(normal_eps), float(color_sharpness), float(mask_sharpness))
+
+
+# ---- image-space loss: weighted L1 + D-SSIM on whole views (rm_image_loss) ----------------------
+
+def _loss_images(out, target, width, height):
+    """out and target as contiguous [V, H, W, 3] float32 views of one device; every check runs on the host
+    before anything reaches the device. Returns (out, target, V)."""
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError(f"width and height must be >= 1, got {width} x {height}")
+    imgs = []
+    for name, t in (("out", out), ("target", target)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch tensor")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
+        if t.dim() not in (2, 4) or t.shape[-1] != 3:
+            raise ValueError(f"{name} must be [V*H*W, 3] or [V, H, W, 3] with 3 channels, got {tuple(t.shape)}")
+        if t.dim() == 4 and tuple(t.shape[1:3]) != (height, width):
+            raise ValueError(f"{name} has shape {tuple(t.shape)}, expected [V, {height}, {width}, 3]")
+        pixels = t.numel() // 3
+        if pixels == 0 or pixels % (width * height) != 0:
+            raise ValueError(f"{name} holds {pixels} pixels, not a positive multiple of "
+                             f"width * height = {width * height} (V*H*W)")
+        imgs.append(t)
+    if imgs[0].numel() != imgs[1].numel():
+        raise ValueError(f"out holds {imgs[0].numel() // 3} pixels and target {imgs[1].numel() // 3}")
+    if imgs[0].device != imgs[1].device:
+        raise ValueError(f"out is on {imgs[0].device} and target on {imgs[1].device}")
+    if not imgs[0].is_cuda:
+        raise ValueError("out and target must be device (HIP) tensors: the loss has no CPU implementation")
+    v = imgs[0].numel() // (3 * width * height)
+    return imgs[0].contiguous().view(v, height, width, 3), imgs[1].contiguous().view(v, height, width, 3), v
+
+
+def image_loss_call(out, target, width, height, *, l1_weight=0.8, ssim_weight=0.2, progress=0.0, plain_l1=False,
+                    inv_count=None, c1=1e-4, c2=9e-4, loss=True, view_stats=False, ssim_map=False, grad=False):
+    """One rm_image_loss call: a dict of the requested outputs ("loss" [1], "view_stats" [V, 3],
+    "ssim_map" and "grad" [V, H, W, 3])."""
+    x, y, v = _loss_images(out, target, width, height)
+    if inv_count is None:
+        inv_count = 1.0 / x.numel()
+    dev = x.device
+    res = {}
+    if loss:
+        res["loss"] = torch.empty((1,), device=dev)
+    if view_stats:
+        res["view_stats"] = torch.empty((v, 3), device=dev)
+    if ssim_map:
+        res["ssim_map"] = torch.empty_like(x)
+    if grad:
+        res["grad"] = torch.empty_like(x)
+    params = native.image_loss_params(l1_weight=float(l1_weight), ssim_weight=float(ssim_weight),
+                                      progress=float(progress), c1=float(c1), c2=float(c2),
+                                      flags=native.RM_LOSS_PLAIN_L1 if plain_l1 else 0)
+    ctx = context(dev)
+    ctx.check(ctx._lib.rm_image_loss(ctx.handle, _ptr(x), _ptr(y), v, int(width), int(height), float(inv_count),
+                                     ctypes.byref(params), _ptr(res.get("loss")), _ptr(res.get("view_stats")),
+                                     _ptr(res.get("ssim_map")), _ptr(res.get("grad"))), "rm_image_loss")
+    return res
+
+
+class _ImageLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, out, target, width, height, kw):
+        need = out.requires_grad
+        res = image_loss_call(out.detach(), target.detach(), width, height, grad=need, **kw)
+        ctx.shape = out.shape
+        if need:
+            ctx.save_for_backward(res["grad"])
+        return res["loss"].reshape(())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        (g,) = ctx.saved_tensors
+        return (g * grad_loss).reshape(ctx.shape), None, None, None, None
+
+
+def image_loss(out, target, width, height, *, l1_weight=0.8, ssim_weight=0.2, progress=0.0, plain_l1=False,
+               inv_count=None):
+    """The image-space loss of 3D Gaussian splatting on whole views, as a scalar differentiable w.r.t. `out`:
+    inv_count (l1_weight sum W |out - target| + ssim_weight sum (1 - SSIM)), SSIM with the 11 x 11 Gaussian
+    window of sigma 1.5 and zero padding, W compute_loss's weight (10 on the target's foreground, 1 + 4 progress
+    elsewhere; plain_l1: 1). out and target: [V*H*W, 3] or [V, H, W, 3] float32 device tensors in the layout of
+    render_diff_camera / render_diff_cameras / render_diff_sh; inv_count defaults to 1 / (3 V H W), the mean.
+    One rm_image_loss call computes the loss and, when out requires grad, the gradient that backward returns
+    times the incoming scalar; target gets none."""
+    if isinstance(target, torch.Tensor) and target.requires_grad:
+        target = target.detach()
+    kw = {"l1_weight": float(l1_weight), "ssim_weight": float(ssim_weight), "progress": float(progress),
+          "plain_l1": bool(plain_l1), "inv_count": inv_count}
+    _loss_images(out, target, width, height)  # the checks, before autograd sees anything
+    return _ImageLossFn.apply(out, target, int(width), int(height), kw)
+
+
+def image_metrics(out, target, width, height):
+    """Per-view image quality on the device: {"psnr": [V], "ssim": [V], "l1": [V]}. PSNR is
+    -10 log10(mean (out - target)^2) for peak 1 (inf for identical images), SSIM the mean of the SSIM map, l1 the
+    mean |out - target|; formed from rm_image_loss's per-view sums (no gradient kernel runs)."""
+    st = image_loss_call(out, target, width, height, plain_l1=True, loss=False, view_stats=True)["view_stats"]
+    n = 3.0 * int(width) * int(height)
+    return {"psnr": -10.0 * torch.log10(st[:, 1] / n), "ssim": st[:, 2] / n, "l1": st[:, 0] / n}
 
 
 def train_step(ray_org, ray_dir, targets, scene: Scene, smooth_k, progress, steps=40, *, inv_count=None,

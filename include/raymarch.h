@@ -334,6 +334,51 @@ int rm_train_step_camera(rm_context* ctx, const rm_camera* cams, int32_t num_vie
                          const rm_scene* scene, const rm_march* march, const rm_grads* grads,
                          float* loss_sum, float* out, int32_t accumulate);
 
+/* ---- image-space loss: weighted L1 + D-SSIM over whole views --------------- */
+/* The loss of 3D Gaussian splatting, (1 - lambda) L1 + lambda (1 - SSIM), on rendered views, with its
+ * gradient and the sums behind PSNR / SSIM / L1. x = out is the rendered image and y = targets the
+ * target, both DEVICE fp32 [V, H, W, 3] in the layout rm_render_diff_camera writes: pixel (v, row, col)
+ * at ((v*H + row)*W + col)*3 + c.
+ *   window    w(i, j) = g(i) g(j), g the 11-tap Gaussian of sigma 1.5 normalised to sum 1 (separable)
+ *   padding   pixels outside an image are zeros (conv2d(padding = 5)); every view and every channel is
+ *             its own image, nothing is read across a view boundary
+ *   per pixel and channel, with F(a) = sum w a over the window:
+ *     mux = F(x), muy = F(y), sx = F(x^2) - mux^2, sy = F(y^2) - muy^2, sxy = F(xy) - mux muy
+ *     S = (2 mux muy + c1)(2 sxy + c2) / ((mux^2 + muy^2 + c1)(sx + sy + c2))
+ *   L1 term   W |x - y|, W compute_loss's weight of the TARGET pixel exactly as the train step forms it:
+ *             (t0 + t1 + t2) > 0.01f ? 10 : fmaf(progress, 4, 1); with RM_LOSS_PLAIN_L1, W = 1. sign(0) = 0.
+ *   loss = inv_count * (l1_weight * sum W|x - y| + ssim_weight * sum (1 - S)), the sums over every pixel
+ *   and channel of the call. inv_count = 1 / (3 V H W) gives the mean; a caller that splits a step over
+ *   calls or ranks passes the global count and the losses (and gradients) add: rm_train_step's convention.
+ *   grad_out = d loss / d x with y held constant:
+ *     L1 part    W * sign(x - y) * s, s = l1_weight * inv_count formed once on the host in float (for
+ *                l1_weight = 1 bit for bit the seed rm_train_step forms)
+ *     SSIM part  with B = dS/dsx, C = dS/dsxy, A = dS/dmux - 2 mux B - muy C:
+ *                d(sum S)/dx_p = sum_q w(q - p) (A_q + 2 x_p B_q + y_p C_q), scaled by -ssim_weight * inv_count.
+ * Outputs, all DEVICE and nullable, at least one required: loss (1 float); view_stats [V][3] = per view
+ * sum W|x - y|, sum (x - y)^2, sum S; ssim_map [V, H, W, 3] = S; grad_out [V, H, W, 3], overwritten.
+ * grad_out NULL: the gradient kernel does not run (the metrics path). num_views, width, height >= 1: no
+ * view cap and no multiple-of-16 rule. The weights are finite and >= 0, c1 and c2 finite and > 0, flags
+ * RM_LOSS_* only; grad_out and ssim_map must not overlap out, targets or each other. Anything else:
+ * RM_ERR_INVALID_ARG with the field named in rm_last_error, before any launch. params NULL: the defaults.
+ * The per-view sums are the fp64 sum of the tiles' partial sums in tile order, rounded once to float, and
+ * the loss the fp64 sum of those over the views: no floating-point atomics, two calls give the same bits,
+ * and an output's bits do not depend on which other outputs are requested. Scratch (three image-sized
+ * arrays when a gradient with ssim_weight > 0 is asked for) is the context's: the first call of a shape
+ * grows it, later calls allocate nothing and never synchronise. */
+#define RM_LOSS_PLAIN_L1 1
+typedef struct rm_image_loss_params {
+  float l1_weight;    /* 0.8 */
+  float ssim_weight;  /* 0.2 */
+  float progress;     /* compute_loss's background weight 1 + 4 progress (0) */
+  float c1, c2;       /* 1e-4, 9e-4 */
+  int32_t flags;      /* RM_LOSS_* */
+} rm_image_loss_params;
+void rm_image_loss_default(rm_image_loss_params* p);   /* 0.8, 0.2, 0, 1e-4, 9e-4, 0 */
+int rm_image_loss(rm_context* ctx, const float* out, const float* targets, int32_t num_views, int32_t width,
+                  int32_t height, float inv_count, const rm_image_loss_params* params, float* loss,
+                  float* view_stats, float* ssim_map, float* grad_out);
+
 /* ---- non-differentiable target renderer: renderer.rs:4-80 (used by generate.rs) ---- */
 /* 40 march steps at k = 32, detached normal, fixed light (-0.5, 0.5, -1)/|.|, lighting =
  * diffuse + 0.1, colour = sum(col exp(-10 d)) / (sum(exp(-10 d)) + 1e-5), mask = exp(-10 D^2).
