@@ -226,7 +226,12 @@ int rm_debug_order_counts(rm_context* ctx, int32_t* counts, int32_t capacity, in
   if (next_set) *next_set = host[3 * kOrderCntStride];
   if (counts)
     for (int st = 0; st < 3; ++st)
-      for (int c = 0; c < kCls; ++c) counts[st * kCls + c] = host[st * kOrderCntStride + c * kOrderClsStride];
+      for (int l = 0; l < kOrderLists; ++l) {  // the last class: the sum of its per-XCD lists
+        const int c = std::min(l, kCls - 1);
+        counts[st * kCls + c] = (l > c ? counts[st * kCls + c] : 0) + host[st * kOrderCntStride + l * kOrderClsStride];
+        if (l >= kCls - 1 && capacity >= 3 * kCls + 3 * kOrderShards)  // the last class's lists one by one
+          counts[3 * kCls + st * kOrderShards + (l - (kCls - 1))] = host[st * kOrderCntStride + l * kOrderClsStride];
+      }
   return RM_OK;
 }
 

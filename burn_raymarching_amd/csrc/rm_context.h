@@ -63,8 +63,8 @@ struct rm_context {
   DevBuf opt_arrival;   // rm_train_step_camera_adam: the reduction's column-block counter
   DevBuf opt_pre;       // rm_train_iteration: the optimizer part of the launch's extra block
   DevBuf block_order;   // centre-out tile order for order_tx x order_ty tiles
-  DevBuf olist;         // cost-ordered dispatch: 3 x [class][kMaxBlocksPerLaunch] block lists
-  DevBuf ocnt;          // 3 x [class] list lengths (zeroed one launch ahead), then the turn word
+  DevBuf olist;         // cost-ordered dispatch: 3 x [list][kMaxBlocksPerLaunch] block lists (kOrderLists)
+  DevBuf ocnt;          // 3 x [list] list lengths (zeroed one launch ahead), then the turn word
   DevBuf cams_dev;      // camera bases of calls with > kInlineCams views (device)
   rm::CamBasis* cams_pin = nullptr;       // their pinned host staging, kCamRing slots
   hipEvent_t cam_ev[kCamRing] = {};       // slot k's copy has run

@@ -489,6 +489,18 @@ bool tile_proof_policy(const KArgs& a, const ProofTier& proof, long long nr) {
   return proof.tier == ProofTier::kLattice && a.tiling == 2 && (nr >= kTileProofMinRays || proof.forced);
 }
 
+// Whether a cost-ordered launch of nb blocks shards its last cost class over kOrderShards lists (the high half
+// of KArgs::order_views, order_append): from kOrderShardMinBlocks blocks on (20 views of 512x512, the tile proof's
+// threshold); env RM_ORDER_SHARDS=0 never, =1 at any size (read once per call). Measured against one list
+// (profiles/r27_order_shards.txt): 80 views +0.6 to +0.8 %, 10 views a tie either way; a launch below the threshold
+// appends to one list and looks its position up in the first kOrderClasses lists alone, as before the shards.
+constexpr long long kOrderShardMinBlocks = 20480;
+int order_shard_policy(long long nb) {
+  const char* e = std::getenv("RM_ORDER_SHARDS");
+  const bool never = e && e[0] == '0', forced = e && e[0] == '1';
+  return !never && (nb >= kOrderShardMinBlocks || forced) ? kOrderShards - 1 : 0;
+}
+
 // The tile proof of one per-ray launch of nb blocks and nr rays (KArgs::tile_proof; rm_tile_proof_kernel), where
 // the policy takes it: a byte per wave of the launch, written on the call's stream after the lattice and the
 // origin kernel and before the per-ray launch, which reads it. Nothing of it is kept: every launch writes all
@@ -860,14 +872,17 @@ int bind_cost_order(rm_context* ctx, const Call& c, const Launch& l, KArgs& a) {
   a.ocnt_w = nullptr;
   a.ocnt_z = nullptr;
   a.oturn = nullptr;
+  a.order_views &= 0xFFFF;
   if (!c.has_bwd()) return RM_OK;
   unsigned long long key = 0;
   if (a.block_order != nullptr && l.nb == l.blocks_left && l.done == 0 && (c.march->flags & RM_MARCH_STATIC_ORDER) == 0) {
     key = ((unsigned long long)c.W << 48) ^ ((unsigned long long)c.H << 32) ^ ((unsigned long long)c.views << 24) ^
           ((unsigned long long)a.Mpad << 1) ^ 1ull ^ ((unsigned long long)(a.split != 0) << 2);
-    constexpr int kCls = kOrderClasses;
+    const int shard_mask = order_shard_policy(l.nb);
+    a.order_views |= shard_mask << 16;
+    key ^= (unsigned long long)(shard_mask != 0) << 3;  // lists appended sharded are read sharded
     int rc;
-    if ((rc = ctx->olist.ensure(ctx, sizeof(int) * 3 * kCls * kMaxBlocksPerLaunch, "cost-order lists")) != RM_OK) return rc;
+    if ((rc = ctx->olist.ensure(ctx, sizeof(int) * 3 * kOrderLists * kMaxBlocksPerLaunch, "cost-order lists")) != RM_OK) return rc;
     // the three sets' counts, then the turn word, kOrderCntStride ints apart
     if ((rc = ctx->ocnt.ensure(ctx, sizeof(int) * 4 * kOrderCntStride, "cost-order counts", true)) != RM_OK) return rc;
     int* olist = ctx->olist.as<int>();

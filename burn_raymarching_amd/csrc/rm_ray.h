@@ -203,7 +203,7 @@ __device__ __forceinline__ void ray_body(const KArgs& a) {
   // ---- escape skip (RM_MARCH_SKIP_ESCAPED): a block whose rays all provably leave the scene
   // (rm_escape_kernel) gets out = 0 and zero gradients without marching -- exactly what the full
   // computation yields for them, since their silhouette mask is 0 in f32 (see escapes()).
-  if (a.ocnt_z != nullptr && blockIdx.x == 0 && tid < kOrderClasses) order_sets(a).cnt_z[tid * kOrderClsStride] = 0;
+  if (a.ocnt_z != nullptr && blockIdx.x == 0 && tid < kOrderLists) order_sets(a).cnt_z[tid * kOrderClsStride] = 0;
   if (a.esc_flags != nullptr && blk >= 0 && a.esc_flags[blk]) {
     if (a.stats != nullptr && tid == 0) atomicAdd(a.stats, 1ull);
     if (a.ocnt_w != nullptr && tid == 0) order_append(a, blk, 0);

@@ -42,6 +42,7 @@ RM_MARCH_NATURAL_ORDER = 8
 RM_MARCH_VALU_ONLY = 16
 RM_MARCH_PER_RAY_ORIGIN = 32
 RM_MARCH_STATIC_ORDER = 64
+RM_ORDER_SHARDS = 4
 RM_MARCH_FORCE_MAX_SHIFT = 128
 RM_MARCH_COLOR_F16 = 256
 RM_MARCH_SPLIT = 512
@@ -258,6 +259,15 @@ class Context:
                    "rm_debug_order_counts")
         c = cls.value
         return [list(buf[i * c:(i + 1) * c]) for i in range(3)], nxt.value
+
+    def order_shard_counts(self):
+        """rm_debug_order_counts: [3][RM_ORDER_SHARDS] block counts of the last cost class's lists, per set."""
+        buf = (_I32 * 256)()
+        cls = _I32()
+        self.check(self._lib.rm_debug_order_counts(self.handle, buf, 256, ctypes.byref(cls), None),
+                   "rm_debug_order_counts")
+        base = 3 * cls.value
+        return [list(buf[base + i * RM_ORDER_SHARDS:base + (i + 1) * RM_ORDER_SHARDS]) for i in range(3)]
 
     def tile_proof(self, capacity: int = 1 << 20) -> bytes:
         """rm_debug_tile_proof: the per-wave bytes of the context's last per-ray launch (1: the pre-pass

@@ -553,7 +553,11 @@ int rm_debug_intermediates(rm_context* ctx, const float* ray_org, const float* r
  * appends to (it reads set (next_set + 2) % 3, whose total equals the launch's block count
  * when the cost order is used and differs when the launch falls back to the static order).
  * Environment RM_DEBUG_SKIP_ORDER_CLEAR=1 makes a launch leave the next set's counts
- * uncleared (the state a failed launch in the rotation leaves), for the recovery test. */
+ * uncleared (the state a failed launch in the rotation leaves), for the recovery test.
+ * The last class's count is the sum of its lists (large launches append it to several; env
+ * RM_ORDER_SHARDS=1 / 0: at any size / never). With capacity >= 3*classes + 3*RM_ORDER_SHARDS the
+ * lists' own counts follow: counts[3*classes + set*RM_ORDER_SHARDS + list]. */
+#define RM_ORDER_SHARDS 4
 int rm_debug_order_counts(rm_context* ctx, int32_t* counts, int32_t capacity, int32_t* classes, int32_t* next_set);
 
 /* The tile proof of the escape lattice (tests): after synchronising the stream, copies the bytes the last

@@ -68,15 +68,53 @@ def run(args):
     fn = lib.rm_debug_block_trace
     fn.restype = ctypes.c_int
     fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]
-    cap = 16384 * 4
+    cap = 131072 * 4  # kMaxBlocksPerLaunch blocks of four waves: an 80-view launch fits
     buf = np.zeros((cap, 12), np.uint64)
     n = ctypes.c_int64()
     ctx.check(fn(ctx.handle, buf.ctypes.data, cap, ctypes.byref(n)), "rm_debug_block_trace")
     tr = buf[:n.value]
-    return tr[tr[:, 0] != 0]  # split blocks of two waves leave the records of waves 2-3 empty
+    # the cost-order counts the traced launch read: its reduction has advanced the turn word to nxt,
+    # so it read set (nxt + 1) % 3 (appended (nxt + 2) % 3; the next launch clears the read set)
+    counts, nxt = ctx.order_counts()
+    read = np.asarray(counts[(nxt + 1) % 3], np.int64)
+    print("cost classes read by the traced launch: " + " ".join(str(int(v)) for v in read))
+    print("cost classes it appended: " + " ".join(str(int(v)) for v in counts[(nxt + 2) % 3]))
+    return tr[tr[:, 0] != 0], read  # split blocks of two waves leave the records of waves 2-3 empty
 
 
-def analyse(tr, bins=40, steps=0):
+def position_classes(pos, counts, grid):
+    """Cost class of every launch position (ray_block): the XCD rotation, then the class-major
+    concatenation of the lists the launch read."""
+    g = pos >> 3
+    b = np.where((g + 1) * 8 <= grid, (g << 3) + (((pos & 7) + g) & 7), pos)
+    return np.searchsorted(np.cumsum(counts), b, side="right")
+
+
+def class_windows(s, e, pos, xcc, simd_key, nsimd, counts):
+    """Per cost class: block count, when its first and last waves start and its last wave ends, its
+    window's share of the launch span, and the mean live waves per SIMD (of every class) inside it.
+    Per XCD: the last wave's end."""
+    span = e.max()
+    grid = int(pos.max()) + 1
+    if int(counts.sum()) != grid:
+        print(f"class counts sum to {int(counts.sum())}, the grid is {grid}: static order, no class windows")
+    else:
+        cls = position_classes(pos, counts, grid)
+        print(" class  blocks  first start  last start  last end (us)  window/span  live/SIMD in window")
+        for c in range(len(counts)):
+            m = cls == c
+            if not m.any():
+                continue
+            a, b = s[m].min(), e[m].max()
+            ov = np.clip(np.minimum(e, b) - np.maximum(s, a), 0, None)
+            print(f" {c:5d}  {int(counts[c]):6d}  {a:11.1f}  {s[m].max():10.1f}  {b:8.1f}       {(b - a) / span:10.3f}"
+                  f"  {ov.sum() / max(b - a, 1e-9) / nsimd:8.2f}")
+    ends = [e[xcc == x].max() for x in np.unique(xcc)]
+    print("XCD last-wave end us: " + " ".join(f"{x}:{v:.1f}" for x, v in zip(np.unique(xcc), ends))
+          + f"  (skew {max(ends) - min(ends):.1f} us, {(max(ends) - min(ends)) / span:.3f} of the span)")
+
+
+def analyse(tr, bins=40, steps=0, counts=None):
     t0, t1 = tr[:, 0].astype(np.int64), tr[:, 1].astype(np.int64)
     base = t0.min()
     s, e = (t0 - base) / 100.0, (t1 - base) / 100.0  # microseconds (100 MHz)
@@ -119,6 +157,8 @@ def analyse(tr, bins=40, steps=0):
         cu_end[k] = max(cu_end.get(k, 0.0), v)
     ce = np.array(sorted(cu_end.values()))
     print("CU last-wave end us  min/10/50/90/max: " + " ".join(f"{np.percentile(ce, p):.1f}" for p in (0, 10, 50, 90, 100)))
+    if counts is not None:
+        class_windows(s, e, pos, xcc, simd_key, nsimd, counts)
     if tr.shape[1] >= 8 and steps:
         tm = (tr[:, 4].astype(np.int64) - base) / 100.0
         tp = (tr[:, 5].astype(np.int64) - base) / 100.0
@@ -177,10 +217,14 @@ def main():
     ap.add_argument("--cameras", default="", help="cameras.json poses instead of the ring (bench.py --cameras)")
     ap.add_argument("--color-f16", action="store_true")
     args = ap.parse_args()
-    tr = np.load(args.load)["trace"] if args.load else run(args)
+    if args.load:
+        z = np.load(args.load)
+        tr, counts = z["trace"], (z["counts"] if "counts" in z else None)
+    else:
+        tr, counts = run(args)
     if args.out:
-        np.savez_compressed(args.out, trace=tr)
-    analyse(tr, args.bins, args.march_steps)
+        np.savez_compressed(args.out, trace=tr, **({} if counts is None else {"counts": counts}))
+    analyse(tr, args.bins, args.march_steps, counts)
 
 
 if __name__ == "__main__":
