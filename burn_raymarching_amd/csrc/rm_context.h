@@ -36,6 +36,15 @@ struct DevBuf {
 
 constexpr int kCamRing = 32;  // calls of > kInlineCams views in flight before the host waits for a slot
 
+// The centre-out block order of one tiling (ensure_block_order): written once, when the context first meets
+// a tiled call of tx x ty tiles and `sub` blocks a tile, and never rewritten or freed before the context, so a
+// launch that holds its address -- in flight, or captured in a hipGraph -- reads its own order whatever other
+// tilings later calls bring.
+struct BlockOrder {
+  int tx = 0, ty = 0, sub = 0;
+  DevBuf table;  // tx * ty * sub ints
+};
+
 }  // namespace
 
 struct rm_context {
@@ -62,7 +71,7 @@ struct rm_context {
   DevBuf red_arrivals;  // rm_reduce_partials' per-column-block arrival counters
   DevBuf opt_arrival;   // rm_train_step_camera_adam: the reduction's column-block counter
   DevBuf opt_pre;       // rm_train_iteration: the optimizer part of the launch's extra block
-  DevBuf block_order;   // centre-out tile order for order_tx x order_ty tiles
+  std::list<BlockOrder> block_orders;  // centre-out tile orders, one per tiling the context has met
   DevBuf olist;         // cost-ordered dispatch: 3 x [list][kMaxBlocksPerLaunch] block lists (kOrderLists)
   DevBuf ocnt;          // 3 x [list] list lengths (zeroed one launch ahead), then the turn word
   DevBuf cams_dev;      // camera bases of calls with > kInlineCams views (device)
@@ -79,7 +88,6 @@ struct rm_context {
   bool adam_done = false;      // the last call's optimizer ran inside its reduction
   long long stats_blocks = 0;  // ray blocks launched while stats are on
   long long stats_waves = 0;   // their ray waves (a split block holds one)
-  int order_tx = 0, order_ty = 0, order_sub = 0;
   int* stall_flag = nullptr;        // rm_debug_stall: host-mapped release flag (host pointer)
   int* oturn = nullptr;             // device word in ocnt: the list set the next keyed launch appends to
   unsigned long long cost_key = 0;  // geometry of the last keyed launch (its lists order the next)

@@ -815,9 +815,15 @@ bool march_policy(const Call& c, long long n, KArgs& a, ProofTier& proof) {
 // Centre-out dispatch order of the ray blocks of a view's tx x ty 16x16 tiles (ray_block): by
 // distance of the block's pixel-centre from the image centre, ties by block index. A block is a
 // whole tile (256-ray blocks) or one of its four 8x8 quadrants (64-ray blocks: the split march), in
-// the pixel order of setup_ray. Built once per image size.
-int ensure_block_order(rm_context* ctx, int tx, int ty, int sub) {
-  if (ctx->block_order && ctx->order_tx == tx && ctx->order_ty == ty && ctx->order_sub == sub) return RM_OK;
+// the pixel order of setup_ray. Built once per tiling (tx, ty, sub) and context, each in a table of its own
+// that nothing rewrites (BlockOrder): calls of different image sizes or block sizes alternate on one context
+// without a launch in flight, or a captured one, ever reading another tiling's order.
+int ensure_block_order(rm_context* ctx, int tx, int ty, int sub, const int** table) {
+  for (const BlockOrder& o : ctx->block_orders)
+    if (o.tx == tx && o.ty == ty && o.sub == sub) {
+      *table = o.table.as<int>();
+      return RM_OK;
+    }
   // sub = ray blocks per 16x16 tile: 1 (256-ray blocks), 4 (8x8 quadrants: 64-ray split blocks),
   // 8 (8x4 halves of the quadrants: 32-ray split blocks) or 16 (8x2 quarters: 16-ray split blocks)
   std::vector<int> ord((size_t)tx * ty * sub);
@@ -832,14 +838,30 @@ int ensure_block_order(rm_context* ctx, int tx, int ty, int sub) {
     return dx * dx + dy * dy;
   };
   std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return key(x) < key(y); });
-  // launches in flight read the previous order: drain them before the table is rewritten
-  if (ctx->block_order) RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // a new table: no launch knows its address yet, so nothing is drained. Not under capture (an allocation
+  // and a copy): a captured call finds the table an eager call of its tiling made.
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  RM_HIP(ctx, hipStreamIsCapturing(ctx->stream, &cap));
+  if (cap != hipStreamCaptureStatusNone)
+    return fail(ctx, RM_ERR_UNSUPPORTED,
+                "a captured call of %d x %d tiles needs the context's block order: run the same call once before "
+                "the capture", tx, ty);
+  ctx->block_orders.emplace_back();
+  BlockOrder& o = ctx->block_orders.back();
   int rc;
-  if ((rc = ctx->block_order.ensure(ctx, sizeof(int) * ord.size(), "block order")) != RM_OK) return rc;
-  RM_HIP(ctx, hipMemcpy(ctx->block_order.p, ord.data(), sizeof(int) * ord.size(), hipMemcpyHostToDevice));
-  ctx->order_tx = tx;
-  ctx->order_ty = ty;
-  ctx->order_sub = sub;
+  if ((rc = o.table.ensure(ctx, sizeof(int) * ord.size(), "block order")) != RM_OK) {
+    ctx->block_orders.pop_back();
+    return rc;
+  }
+  const hipError_t e = hipMemcpy(o.table.p, ord.data(), sizeof(int) * ord.size(), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    ctx->block_orders.pop_back();
+    return fail(ctx, RM_ERR_HIP, "block order upload: %s", hipGetErrorString(e));
+  }
+  o.tx = tx;
+  o.ty = ty;
+  o.sub = sub;
+  *table = o.table.as<int>();
   return RM_OK;
 }
 
@@ -857,8 +879,9 @@ int bind_block_order(rm_context* ctx, const Call& c, const Launch& l, KArgs& a) 
         (c.march->flags & RM_MARCH_NATURAL_ORDER) == 0))
     return RM_OK;
   int rc;
-  if ((rc = ensure_block_order(ctx, c.W / 16, c.H / 16, 256 / l.rpb)) != RM_OK) return rc;
-  a.block_order = ctx->block_order.as<int>();
+  const int* table = nullptr;
+  if ((rc = ensure_block_order(ctx, c.W / 16, c.H / 16, 256 / l.rpb, &table)) != RM_OK) return rc;
+  a.block_order = table;
   a.order_views = (int)(l.nr / npix);
   a.order_tiles = (int)(npix / l.rpb);
   return RM_OK;
