@@ -232,37 +232,76 @@ def render_diff_backward_cameras(cams, width, height, scene: Scene, smooth_k, gr
     return grad_cams
 
 
+def _check_shape(t, name, accepted):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor")
+    if tuple(t.shape) not in accepted:
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected " + " or ".join(str(a) for a in accepted))
+
+
+def _check_param_shapes(centers, radius, light_dir=None, ambient=None):
+    """The shapes the autograd functions take for the per-scene parameters, checked before autograd sees
+    anything (Scene itself flattens whatever has the right number of elements): radius [M] or [M, 1],
+    light_dir [3] or [1, 3], ambient [1] or 0-d. Their gradients come back in the shape passed."""
+    m = centers.shape[0] if isinstance(centers, torch.Tensor) and centers.dim() else 0
+    _check_shape(centers, "centers", ((m, 3),))
+    _check_shape(radius, "radius", ((m,), (m, 1)))
+    if light_dir is not None:
+        _check_shape(light_dir, "light_dir", ((3,), (1, 3)))
+        _check_shape(ambient, "ambient", ((1,), ()))
+
+
+def _rays(ray_org, ray_dir):
+    """The rays as the kernels read them: contiguous float32 [N, 3] (the caller's own tensors where they
+    already are, copies otherwise)."""
+    n = ray_org.shape[0] if isinstance(ray_org, torch.Tensor) and ray_org.dim() else 0
+    return _f32(ray_org, (n, 3), "ray_org"), _f32(ray_dir, (n, 3), "ray_dir")
+
+
+def _scene_tensors(scene: Scene):
+    """What an autograd Function saves of its scene: the five tensors the kernels read. Saved through
+    save_for_backward they carry the version of the caller's parameters wherever they alias them, so an
+    in-place update between forward and backward raises instead of differentiating the new values."""
+    return scene.centers, scene.colors, scene.radius, scene.light_dir, scene.ambient
+
+
+def _scene_grads(g, shapes):
+    """(centers, colors, radius, light_dir, ambient) gradients of the dict g (None where absent), the last
+    three in the shapes the caller passed (radius [M] or [M, 1], light_dir [3] or [1, 3], ambient [1] or 0-d)."""
+    gr, gl, ga = g.get("radius"), g.get("light_dir"), g.get("ambient")
+    return (g.get("centers"), g.get("colors"), gr.reshape(shapes[0]) if gr is not None else None,
+            gl.reshape(shapes[1]) if gl is not None else None, ga.reshape(shapes[2]) if ga is not None else None)
+
+
 class _RenderDiffFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps, normal_eps,
                 color_sharpness, mask_sharpness):
         scene = Scene(centers.detach(), colors.detach(), radius.detach(), light_dir.detach(), ambient.detach())
+        ray_org, ray_dir = _rays(ray_org.detach(), ray_dir.detach())
         ctx.consts = {"normal_eps": normal_eps, "color_sharpness": color_sharpness, "mask_sharpness": mask_sharpness}
-        out, t = render_diff_forward(ray_org.detach(), ray_dir.detach(), scene, smooth_k, steps, return_t=True,
-                                     **ctx.consts)
-        ctx.save_for_backward(ray_org, ray_dir, t)
-        ctx.scene = scene
+        out, t = render_diff_forward(ray_org, ray_dir, scene, smooth_k, steps, return_t=True, **ctx.consts)
+        ctx.save_for_backward(ray_org, ray_dir, t, *_scene_tensors(scene))
         ctx.smooth_k = smooth_k
         ctx.steps = steps
-        ctx.radius_shape = radius.shape
-        ctx.ambient_shape = ambient.shape
+        ctx.shapes = (radius.shape, light_dir.shape, ambient.shape)
         return out
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        ray_org, ray_dir, t = ctx.saved_tensors
+        ray_org, ray_dir, t, *saved = ctx.saved_tensors
+        scene = Scene(*saved)
         grad_out = grad_out.contiguous().float()
         need = ctx.needs_input_grad
         g_org = g_dir = None
         if need[0] or need[1]:
-            g_org, g_dir = render_diff_backward_rays(ray_org, ray_dir, ctx.scene, ctx.smooth_k, grad_out, ctx.steps,
+            g_org, g_dir = render_diff_backward_rays(ray_org, ray_dir, scene, ctx.smooth_k, grad_out, ctx.steps,
                                                      t_march=t, want_org=need[0], want_dir=need[1], **ctx.consts)
         if not any(need[2:7]):  # only the rays are differentiated: the parameter backward does not run
             return (g_org, g_dir) + (None,) * 10
-        g = render_diff_backward(ray_org, ray_dir, ctx.scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t,
-                                 **ctx.consts)
-        return (g_org, g_dir, g["centers"], g["colors"], g["radius"].reshape(ctx.radius_shape), g["light_dir"],
-                g["ambient"].reshape(ctx.ambient_shape), None, None, None, None, None)
+        g = render_diff_backward(ray_org, ray_dir, scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t, **ctx.consts)
+        return (g_org, g_dir) + _scene_grads(g, ctx.shapes) + (None,) * 5
 
 
 def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, smooth_k, steps=40, *,
@@ -270,7 +309,12 @@ def render_diff(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, s
     """renderer_diff.rs:6-91 on the GPU. Differentiable w.r.t. centers, colors, radius, light_dir,
     ambient and, when they require grad, ray_org / ray_dir (see render_diff_backward_rays: the
     reference graph's gradient -- march detached, normal detached -- not the derivative of the
-    image). A caller who differentiates only the scene runs the parameter backward alone."""
+    image). A caller who differentiates only the scene runs the parameter backward alone.
+
+    First order only. The backward reads the caller's own tensors wherever they were contiguous float32 (no
+    copy is made), so an in-place change of one of them between forward and backward raises torch's "modified by
+    an inplace operation" error. radius [M] or [M, 1], light_dir [3] or [1, 3], ambient [1] or 0-d."""
+    _check_param_shapes(centers, radius, light_dir, ambient)
     return _RenderDiffFn.apply(ray_org, ray_dir, centers, colors, radius, light_dir, ambient, float(smooth_k),
                                int(steps), float(normal_eps), float(color_sharpness), float(mask_sharpness))
 
@@ -284,27 +328,27 @@ class _RenderDiffCamerasFn(torch.autograd.Function):
         cams = [(e[i], tg[i], f[i]) for i in range(len(f))]
         ctx.consts = {"normal_eps": normal_eps, "color_sharpness": color_sharpness, "mask_sharpness": mask_sharpness}
         out, t = render_diff_camera(cams, width, height, scene, smooth_k, steps, return_t=True, **ctx.consts)
-        ctx.save_for_backward(t)
+        ctx.save_for_backward(t, *_scene_tensors(scene))
         ctx.cams = cams
         ctx.size = (width, height)
-        ctx.scene = scene
         ctx.smooth_k = smooth_k
         ctx.steps = steps
-        ctx.radius_shape = radius.shape
-        ctx.ambient_shape = ambient.shape
+        ctx.shapes = (radius.shape, light_dir.shape, ambient.shape)
         ctx.cam_meta = (eye.device, eye.dtype, target.device, target.dtype, fov_deg.device, fov_deg.dtype,
                         fov_deg.shape)
         return out
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        (t,) = ctx.saved_tensors
+        t, *saved = ctx.saved_tensors
+        scene = Scene(*saved)
         grad_out = grad_out.contiguous().float()
         need = ctx.needs_input_grad
         w, h = ctx.size
         g_eye = g_tgt = g_fov = None
         if need[0] or need[1] or need[2]:
-            gc = render_diff_backward_cameras(ctx.cams, w, h, ctx.scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t,
+            gc = render_diff_backward_cameras(ctx.cams, w, h, scene, ctx.smooth_k, grad_out, ctx.steps, t_march=t,
                                               **ctx.consts)
             ed, et, td, tt, fd, ft, fs = ctx.cam_meta
             g_eye = gc[:, 0:3].to(device=ed, dtype=et) if need[0] else None
@@ -316,12 +360,11 @@ class _RenderDiffCamerasFn(torch.autograd.Function):
             v, npix = len(ctx.cams), w * h
             for i in range(0, v, native.RM_MAX_VIEWS_PER_CALL):  # the parameter backward takes 128 views a call
                 j = min(i + native.RM_MAX_VIEWS_PER_CALL, v)
-                gi = render_diff_backward_camera(ctx.cams[i:j], w, h, ctx.scene, ctx.smooth_k,
+                gi = render_diff_backward_camera(ctx.cams[i:j], w, h, scene, ctx.smooth_k,
                                                  grad_out[i * npix:j * npix], ctx.steps, t_march=t[i * npix:j * npix],
                                                  **ctx.consts)
                 g = gi if g is None else {k: g[k] + gi[k] for k in g}
-            gs = (g["centers"], g["colors"], g["radius"].reshape(ctx.radius_shape), g["light_dir"],
-                  g["ambient"].reshape(ctx.ambient_shape))
+            gs = _scene_grads(g, ctx.shapes)
         return (g_eye, g_tgt, g_fov, None, None) + gs + (None,) * 5
 
 
@@ -336,7 +379,14 @@ def render_diff_cameras(eye, target, fov_deg, width, height, centers, colors, ra
     the image: it follows finite differences for a rigid shift of the camera (eye and target moved
     together; measured cosines 0.89 to 0.99) and so serves pose refinement of that kind, but it need
     not for eye moved alone against a fixed target, where the translation and rotation parts
-    nearly cancel (one of three measured cases gave a cosine of -0.93)."""
+    nearly cancel (one of three measured cases gave a cosine of -0.93). First order only; the scene tensors
+    are held as render_diff holds them, the camera tensors are read at forward time."""
+    _check_param_shapes(centers, radius, light_dir, ambient)
+    v = eye.shape[0] if isinstance(eye, torch.Tensor) and eye.dim() else 0
+    for name, t, shape in (("eye", eye, (v, 3)), ("target", target, (v, 3)), ("fov_deg", fov_deg, (v,))):
+        _check_shape(t, name, (shape,))
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name} must be float32, got {t.dtype}")
     return _RenderDiffCamerasFn.apply(eye, target, fov_deg, int(width), int(height), centers, colors, radius,
                                       light_dir, ambient, float(smooth_k), int(steps), float(normal_eps),
                                       float(color_sharpness), float(mask_sharpness))
@@ -370,7 +420,7 @@ def render_diff_backward_camera(cams, width, height, scene: Scene, smooth_k, gra
                                 normal_eps=1e-4, color_sharpness=10.0, mask_sharpness=15.0):
     cams = list(cams)
     if len(cams) > native.RM_MAX_VIEWS_PER_CALL:
-        raise ValueError("at most 16 views per backward call")
+        raise ValueError(f"at most RM_MAX_VIEWS_PER_CALL = {native.RM_MAX_VIEWS_PER_CALL} views per backward call")
     n = len(cams) * width * height
     grad_out = _f32(grad_out, (n, 3), "grad_out")
     if t_march is not None:
@@ -508,34 +558,33 @@ class _RenderDiffShFn(torch.autograd.Function):
                 color_sharpness, mask_sharpness):
         scene = Scene(centers.detach(), colors.detach(), radius.detach(), light_dir.detach(), ambient.detach())
         ctx.consts = {"normal_eps": normal_eps, "color_sharpness": color_sharpness, "mask_sharpness": mask_sharpness}
+        ray_org, ray_dir = _rays(ray_org.detach(), ray_dir.detach())
         shd = sh.detach()
-        out, t = render_diff_sh_forward(ray_org.detach(), ray_dir.detach(), scene, shd, smooth_k, steps, return_t=True,
-                                        **ctx.consts)
-        ctx.save_for_backward(ray_org, ray_dir, t, shd)
-        ctx.scene = scene
+        if shd.shape[1]:
+            shd = _f32(shd, (scene.num_spheres, shd.shape[1], 3), "sh")
+        out, t = render_diff_sh_forward(ray_org, ray_dir, scene, shd, smooth_k, steps, return_t=True, **ctx.consts)
+        ctx.save_for_backward(ray_org, ray_dir, t, shd, *_scene_tensors(scene))
         ctx.smooth_k = smooth_k
         ctx.steps = steps
-        ctx.radius_shape = radius.shape
-        ctx.ambient_shape = ambient.shape
+        ctx.shapes = (radius.shape, light_dir.shape, ambient.shape)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
-        ray_org, ray_dir, t, sh = ctx.saved_tensors
+        ray_org, ray_dir, t, sh, *saved = ctx.saved_tensors
+        scene = Scene(*saved)
         need = ctx.needs_input_grad
         names = ("centers", "colors", "sh", "radius", "light_dir", "ambient")
         want = [k for k, w in zip(names, need[2:8]) if w and not (k == "sh" and sh.shape[1] == 0)]
         g = {}
         if want:
-            g = render_diff_sh_backward(ray_org, ray_dir, ctx.scene, sh, ctx.smooth_k, grad_out.contiguous().float(),
+            g = render_diff_sh_backward(ray_org, ray_dir, scene, sh, ctx.smooth_k, grad_out.contiguous().float(),
                                         ctx.steps, t_march=t, want=want, **ctx.consts)
         if need[4] and sh.shape[1] == 0:
             g["sh"] = torch.zeros_like(sh)
-        gr, ga = g.get("radius"), g.get("ambient")
-        return (None, None, g.get("centers"), g.get("colors"), g.get("sh"),
-                gr.reshape(ctx.radius_shape) if gr is not None else None, g.get("light_dir"),
-                ga.reshape(ctx.ambient_shape) if ga is not None else None, None, None, None, None, None)
+        gs = _scene_grads(g, ctx.shapes)
+        return (None, None, gs[0], gs[1], g.get("sh"), gs[2], gs[3], gs[4], None, None, None, None, None)
 
 
 def render_diff_sh(ray_org, ray_dir, centers, colors, sh, radius, light_dir, ambient, smooth_k, steps=40, *,
@@ -552,6 +601,7 @@ def render_diff_sh(ray_org, ray_dir, centers, colors, sh, radius, light_dir, amb
     if any(isinstance(r, torch.Tensor) and r.requires_grad for r in (ray_org, ray_dir)):
         raise ValueError("ray gradients are not available with SH: render_diff_sh does not differentiate ray_org / "
                          "ray_dir (detach them, or use render_diff for the ray and pose gradients)")
+    _check_param_shapes(centers, radius, light_dir, ambient)
     return _RenderDiffShFn.apply(ray_org, ray_dir, centers, colors, sh, radius, light_dir, ambient, float(smooth_k),
                                  int(steps), float(normal_eps), float(color_sharpness), float(mask_sharpness))
 
@@ -938,6 +988,7 @@ def sdf_field(points, centers, colors, radius, smooth_k=32.0, *, color_sharpness
     gradients whose inputs require grad, from the outputs that received one. Half-precision `colors`
     select the fp16 path and receive their float32 gradient cast to half. First order only (no
     gradient through sdf_query's grad output, no double backward)."""
+    _check_param_shapes(centers, radius)
     return _SdfFieldFn.apply(points, centers, colors, radius, float(smooth_k), float(color_sharpness))
 
 

@@ -427,6 +427,10 @@ void rm_view_params_default(rm_view_params* params);   /* 100, 32, 1e-3, 20, 1e-
  * +0.01 of the training activation and the reference viewer draws them so; whether to add it is
  * the caller's business. Outputs (device pointers, any may be NULL but not all three):
  *   out_rgb   [F,H,W,3] linear float RGB;
+ *   (float arrays, here and in every other call of this header, inputs and outputs alike, need the
+ *   4-byte alignment of a float and no more: the kernels read and write the caller's arrays one
+ *   word at a time, so a view that starts an odd number of floats into an allocation is as good
+ *   as the allocation; tests/test_gpu_autograd_contract.py pins the bits for the float32 inputs)
  *   out_rgba8 [F,H,W,4] (4-byte aligned) the bytes the viewer's sRGB surface shows: the piecewise
  *             sRGB encode (12.92 c below 0.0031308, else 1.055 c^(1/2.4) - 0.055) rounded to
  *             nearest, alpha 255 -- not the gamma-1/2.2 truncation of the training PNGs (util.rs);
